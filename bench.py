@@ -17,6 +17,17 @@ Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes
 the search kernel's device time measured with HIP events on its own stream.
 `cpu_baseline` = the oracle's single-thread CDCL restatement ("port": the real
 rustsat-glucose cannot be built here) on a bounded sample of the same workload.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line: `value`,
+`ms_per_step`, the windows and the roofline figures derived from the solver's own counters.  Everything that takes runs of
+its own - the CPU baselines, the exchange-on window, the first-UNSAT ladders (and their sharded form at N > 1 GPUs), the
+measured copy ceiling and the PMC traffic summary attached from profiles/ - runs only with `--full` (left null otherwise).
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0), as float64 .npy files: results.npy
+(the SolverResult code of every instance, k = k_hi..k_lo: 10 SAT, 20 UNSAT, 0 still open), decided.npy (instances
+decided so far), stats.npy (the solver's stats() after that step, every field of solver.Mi355SatStats in its order) and
+step_stats.npy (what the step itself added to each search counter, see STEP_COUNTERS).  The inputs (CNF, assumptions,
+seeds) are the same from run to run for the same arguments; the slices are time-bounded, so how far the search gets in
+a step, and with it every search counter, is not.
 """
 import argparse
 import json
@@ -60,6 +71,23 @@ def measured_copy_gbs(torch, device_index):
     del a, b
     torch.cuda.empty_cache()
     return best
+
+
+# the search counters of Mi355SatStats that one step adds to (step_stats.npy, in this order)
+STEP_COUNTERS = ("propagations", "decisions", "conflicts", "restarts", "learnts", "learnt_literals", "reduce_dbs",
+                 "kernel_launches", "n_deq", "n_watch", "n_cl_lit", "n_move", "n_enq", "bcp_steps", "bcp_requeued")
+
+
+def dump_outputs(out_dir, results, decided, st_before, st_after):
+    """--dump-outputs: what the last timed sweep_step handed its caller and the stats() around it."""
+    import numpy as np
+    from timberborn_support_solver_amd.solver import Mi355SatStats
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "results.npy"), np.array([r.value for r in results], dtype=np.float64))
+    np.save(os.path.join(out_dir, "decided.npy"), np.array([decided], dtype=np.float64))
+    np.save(os.path.join(out_dir, "stats.npy"), np.array([st_after[f] for f, _ in Mi355SatStats._fields_], dtype=np.float64))
+    np.save(os.path.join(out_dir, "step_stats.npy"),
+            np.array([st_after[f] - st_before[f] for f in STEP_COUNTERS], dtype=np.float64))
 
 
 def _spawn_ranks(n):
@@ -119,7 +147,12 @@ def main():
                     "exchange makes the trajectory, and with it the rate, depend on slice timing), 0 on.  The first-UNSAT line always "
                     "runs the product default (exchange on).")
     ap.add_argument("--platforms", default="default", choices=["default", "1x1"])
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: CPU baselines, the "
+                    "exchange-on window, the first-UNSAT ladders, the measured copy ceiling and the attached PMC traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.first_unsat_size is not None:
         args.first_unsat_sizes = str(args.first_unsat_size)
     fu_sizes = [int(x) for x in args.first_unsat_sizes.split(",") if x.strip() and int(x) > 0]
@@ -194,10 +227,12 @@ def main():
     t0 = time.perf_counter()
     decided = 0
     marks = [(t0, st0["propagations"])]          # per-step stamps: the spread of the rate inside the timed region
+    st_prev = st_cur = st0
     for _ in range(args.steps):
         res, decided = solver.sweep_step()
         cut = exchange_cut(res)
-        marks.append((time.perf_counter(), solver.stats()["propagations"]))
+        st_prev, st_cur = st_cur, solver.stats()
+        marks.append((time.perf_counter(), st_cur["propagations"]))
     barrier()
     dt = time.perf_counter() - t0
     st1 = solver.stats()
@@ -224,8 +259,10 @@ def main():
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
     note(f"timed region done: {total_props / max_dt:.3e} propagations/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, decided, st_prev, st_cur)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:   # reported baseline: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:   # reported baseline: rank 0 at N=1 only
         import numpy as np
         from oracle import oracle as ora
         np_lits, np_offs = np.asarray(cnf.lits, dtype=np.int32), np.asarray(cnf.offsets, dtype=np.uint64)
@@ -274,7 +311,7 @@ def main():
     # on, what a worker does in slice n depends on what was collected after slice n - 1, i.e. on slice timing - but
     # reported beside it so that the headline is not mistaken for the default configuration.
     exchange_window = None
-    if rank == 0 and world == 1 and args.share < 0 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and args.share < 0 and not args.no_cpu:
         s2 = Mi355Sat(device=device_index, workers=workers, slice_ms=args.slice_ms, seed=1000, _lib_override=lib_override,
                       var_order=args.var_order, share=0, ramp=-1)
         s2.add_cnf(cnf.lits, cnf.offsets)
@@ -303,7 +340,7 @@ def main():
     # sequential loop (k := count - 1) on the oracle.
     first_unsat = None
     sharded = None
-    if world > 1 and fu_sizes:
+    if args.full and world > 1 and fu_sizes:
         # strong scaling of ONE ladder over the ranks: the bounds k = k_hi - rank - i*world are sharded, the cut
         # (min SAT count, max UNSAT k) and the best model are the only things exchanged; in the replica
         # tail (the last bounds, every rank the same bound) the ranks also pass on the clauses they learn
@@ -326,7 +363,7 @@ def main():
                    "optimum_k": sat[-1]["count"] if ok else None, "gpu_seconds": gpu_s if ok else None,
                    "seconds_to_cut_after_first_bound": st_sh.get("seconds_to_cut"),
                    "ring_records_from_other_ranks": st_sh.get("ring_imported")}
-    if rank == 0 and world == 1 and fu_sizes and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and fu_sizes and not args.no_cpu:
         from oracle import oracle as ora
         from timberborn_support_solver_amd import PlatformLayout, solver_loop_sweep
         first_unsat = []
@@ -371,7 +408,7 @@ def main():
         kern_s = d["kernel_seconds"]
         launches = max(1, d["kernel_launches"])
         achieved = alg_bytes / max(kern_s, 1e-9) / 1e9
-        peak_measured = measured_copy_gbs(torch, device_index)
+        peak_measured = measured_copy_gbs(torch, device_index) if args.full else None
         # HBM bytes per launch of the dominant kernel from the PMC passes (they cannot run inside this process:
         # separate `rocprofv3 --pmc` runs of this same command; the committed summary is attached when this run is
         # the configuration it was taken on)
@@ -382,6 +419,8 @@ def main():
                        args.platforms == "default" and args.share == -1 and args.var_order == 0)
         ident = _build_identity()
         traffic_note = "no PMC summary under profiles/ was taken on this build (kernel sources differ): traffic left null"
+        if not args.full:
+            tfiles, traffic_note = [], "not looked up in a plain run (--full attaches it)"
         for tf in reversed(tfiles):     # attach a PMC summary only if it was measured on THESE kernel sources
             tj = json.load(open(tf))
             if default_cfg and tj.get("kernel_source_sha16") == ident["kernel_source_sha16"]:
@@ -420,13 +459,14 @@ def main():
             "first_unsat_sharded": sharded,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "peak_measured": peak_measured,
-                         "peak_measured_note": "device-to-device copy of 2 GiB on this box (read + write bytes)",
+                         "peak_measured_note": "device-to-device copy of 2 GiB on this box (read + write bytes); --full only",
                          "traffic": traffic, "traffic_source": traffic_src, "traffic_note": traffic_note,
                          "build": ident,
                          "kernel": "ms_search_kernel", "kernel_ms_avg": kern_s / launches * 1e3,
                          "algorithmic_bytes_per_launch": alg_bytes / launches,
                          "bytes_per_propagation": alg_bytes / max(1, props)},
             "cpu_baseline": cpu,
+            "full": args.full,
         }
         print(json.dumps(out))
     if dist is not None:

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-echo "[profile] bench line"; python3 $ROOT/bench.py "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { tail -5 $OUT/${TAG}_bench.err; exit 1; }
+echo "[profile] bench line"; python3 $ROOT/bench.py --full "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { tail -5 $OUT/${TAG}_bench.err; exit 1; }
 cat $OUT/${TAG}_bench.json | head -c 600; echo
 echo "[profile] kernel trace"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_kt -- python3 $ROOT/bench.py --no-cpu "$@" > $OUT/${TAG}_kt.log 2>&1 || { tail -5 $OUT/${TAG}_kt.log; exit 1; }

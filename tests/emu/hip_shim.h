@@ -118,6 +118,13 @@ template <class T>
 static inline T atomicAnd(T* p, T v) { T o = *p; *p = o & v; return o; }
 #define __HIP_MEMORY_SCOPE_AGENT 4
 #define __HIP_MEMORY_SCOPE_WAVEFRONT 2
+// g++ has no __hip_atomic_* builtins; clang (the sanitizer build, asan.mk) has them, with these meanings on the host
+#if defined(__has_builtin)
+#if __has_builtin(__hip_atomic_load)
+#define EMU_HIP_ATOMIC_BUILTINS 1
+#endif
+#endif
+#ifndef EMU_HIP_ATOMIC_BUILTINS
 // (the kernels call these on plain and on volatile-qualified pointers)
 template <class T>
 static inline T __hip_atomic_load(const volatile T* p, int, int) { return *p; }
@@ -134,6 +141,7 @@ static inline bool __hip_atomic_compare_exchange_strong(volatile T* p, T* expect
     *expected = o;
     return false;
 }
+#endif
 // dynamic LDS: one static 160 KiB block per (sequentially executed) workgroup
 #define HIP_DYNAMIC_SHARED(type, var) static thread_local type var[163840 / sizeof(type)];
 

@@ -192,7 +192,7 @@ def test_unsat_verdicts_carry_a_checked_drup_proof(tmp_path, terrain, pset, k):
         assert st["shared_imported"] + st["shared_imported_units"] > 0
 
 
-def test_cpp_solver_loop_cli_prints_the_reference_messages():
+def test_cpp_solver_loop_cli_prints_the_reference_messages(tmp_path):
     """The compiled host side (csrc/host/solver_loop.cpp + cli.cpp) over the C ABI: `rect 8 8 -l1:20`
     is BASELINE.json configs[0] run on the GPU; ex3 from a project file is configs[3]."""
     import os
@@ -207,8 +207,7 @@ def test_cpp_solver_loop_cli_prints_the_reference_messages():
     assert lines[0].startswith("Solution found (") and "Solution validation OK" in lines
     assert "Solution validation FAILED" not in lines
     assert [l for l in lines if l.startswith("Solution found")][-1] == "Solution found (2 platforms total)"   # k* = 2
-    toml = os.path.join(ROOT, "gpurun_out", "ex3_test.toml")
-    os.makedirs(os.path.dirname(toml), exist_ok=True)
+    toml = str(tmp_path / "ex3_test.toml")
     with open(toml, "w") as f:
         f.write("[world]\ngrid = [\n" + "".join(f'    "{r}",\n' for r in terrain_rows("ex3")) + "]\n")
     out = subprocess.run([cli, "file", toml, "-l1:20", "--platforms", "1x1", "--workers", "64"], capture_output=True, text=True, timeout=120)
