@@ -13,9 +13,10 @@
  *   crates/gui/src/main.rs:2,26             App::<GlucoseSimp>
  *
  * rustsat-glucose talks to its C++ solver through an IPASIR-shaped C API
- * (init / add / solve / val / interrupt / release; solve returns 10/20/0).
- * The functions below have the same shape so that a Rust `Solve` impl over
- * this library is a thin clone of that wrapper.
+ * (init / add / assume / solve / val / failed / interrupt / release; solve
+ * returns 10/20/0).  The functions below have the same shape so that a Rust
+ * `Solve` + `SolveIncremental` impl over this library is a thin clone of that
+ * wrapper.
  *
  * Conventions
  *   - literals are IPASIR/DIMACS: +v / -v, v >= 1; 0 terminates a clause in
@@ -191,6 +192,21 @@ int mi355sat_reserve(mi355sat* s, uint64_t n_vars);
 /* Returns MI355SAT_SAT / MI355SAT_UNSAT / MI355SAT_INTERRUPTED or a negative error. */
 int mi355sat_solve(mi355sat* s);
 
+/* --- assumptions and failed-assumption cores (SolveIncremental) ----------- */
+/* IPASIR assume: lit holds for the next mi355sat_solve() only, which consumes the list whatever it returns.  A
+ * variable above the highest one seen is reserved (as mi355sat_reserve).  Assumptions may repeat or contradict each
+ * other. */
+int mi355sat_assume(mi355sat* s, int32_t lit);
+/* IPASIR failed: after mi355sat_solve() returned UNSAT, 1 if lit is in the core, else 0; MI355SAT_ERR_STATE in any
+ * other state (no solve yet, SAT, interrupted, exhausted budget, a clause or an assumption added since). */
+int mi355sat_failed(mi355sat* s, int32_t lit);
+/* The core of the last UNSAT solve(): a subset of the assumptions as the caller gave them, in their order, such that
+ * formula AND core is UNSAT (empty if the formula alone is).  Not minimised.  out may be NULL to size the buffer;
+ * *n receives the length; MI355SAT_ERR_ARG if cap is too small, MI355SAT_ERR_STATE as for mi355sat_failed(). */
+int mi355sat_core(mi355sat* s, int32_t* out, uint64_t cap, uint64_t* n);
+/* The same for instance i of the last mi355sat_solve_batch() that reported UNSAT (MI355SAT_ERR_STATE otherwise). */
+int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n);
+
 /* Batched solve under assumptions: instance i = formula AND assumption literals
  * assumps[assump_offsets[i] .. assump_offsets[i+1]).  This is what the sharded
  * decreasing-k sweep uses: the clause database (base CNF + one totalizer built
@@ -278,7 +294,8 @@ int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_
 int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words, uint64_t* n_records /* may be NULL */);
 
 /* Optional DRUP proof (text, DIMACS literals, one lemma per line, the empty clause last) of the next plain
- * solve(), in its default configuration: all workers, clause exchange on.  Order of the lines: what the
+ * solve() - under assumptions, the clause of the negated core literals instead of the empty clause - in its default
+ * configuration: all workers, clause exchange on.  Order of the lines: what the
  * simplification derived, then after every kernel slice the clauses each worker learnt in it; every line is a
  * RUP consequence of the lines before it (the exchange only hands on clauses of earlier slices).  Deletion lines
  * ("d ...") are written for the clauses a worker drops when it reduces its clause database - except those another

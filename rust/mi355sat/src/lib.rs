@@ -7,11 +7,12 @@
 //! ```
 //!
 //! Trait surface = what the reference exercises: `Default`, `add_cnf` / `add_clause_ref`,
-//! `interrupter`, `solve`, `full_solution` (through `lit_val` + `max_var`), `stats`.
+//! `interrupter`, `solve`, `full_solution` (through `lit_val` + `max_var`), `stats`; plus `SolveIncremental`
+//! (`solve_assumps`, `core`: IPASIR assume / failed) for rustsat's incremental encodings and core-guided code.
 use std::os::raw::{c_char, c_int, c_void};
 
 use rustsat::instances::Cnf;
-use rustsat::solvers::{Interrupt, InterruptSolver, Solve, SolveStats, SolverResult, SolverStats};
+use rustsat::solvers::{Interrupt, InterruptSolver, Solve, SolveIncremental, SolveStats, SolverResult, SolverStats};
 use rustsat::types::{Cl, Clause, Lit, TernaryVal, Var};
 
 /// Mirror of `mi355sat_opts` (include/mi355sat.h); zero = defaults.
@@ -46,6 +47,8 @@ extern "C" {
     fn mi355sat_reserve(s: *mut c_void, n_vars: u64) -> c_int;
     fn mi355sat_solve(s: *mut c_void) -> c_int;
     fn mi355sat_val(s: *mut c_void, lit: i32) -> i32;
+    fn mi355sat_assume(s: *mut c_void, lit: i32) -> c_int;
+    fn mi355sat_core(s: *mut c_void, out: *mut i32, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
 }
@@ -85,6 +88,7 @@ impl Default for Mi355Sat {                    // S::default(): main.rs:295, sol
 impl Drop for Mi355Sat { fn drop(&mut self) { unsafe { mi355sat_free(self.h) } } }
 
 fn ipasir(l: Lit) -> i32 { let v = l.vidx32() as i32 + 1; if l.is_neg() { -v } else { v } }
+fn from_ipasir(l: i32) -> Lit { let v = Var::new(l.unsigned_abs() - 1); if l < 0 { v.neg_lit() } else { v.pos_lit() } }
 
 impl Solve for Mi355Sat {
     fn signature(&self) -> &'static str { "mi355sat (HIP/gfx950 wave-parallel CDCL)" }
@@ -123,6 +127,25 @@ impl Solve for Mi355Sat {
     fn lit_val(&self, lit: Lit) -> anyhow::Result<TernaryVal> {      // full_solution(): main.rs:329, app.rs:154
         let l = ipasir(lit);
         Ok(match unsafe { mi355sat_val(self.h, l) } { v if v == l => TernaryVal::True, 0 => TernaryVal::DontCare, _ => TernaryVal::False })
+    }
+}
+
+/// IPASIR assume / failed, as rustsat-glucose wraps them: the assumptions hold for one `solve_assumps` call; `core`
+/// after an Unsat answer returns the NEGATED failed assumptions - a clause the formula implies (rustsat's convention).
+/// Replayed in C by tests/abi_cores.c.
+impl SolveIncremental for Mi355Sat {
+    fn solve_assumps(&mut self, assumps: &[Lit]) -> anyhow::Result<SolverResult> {
+        for l in assumps {
+            if unsafe { mi355sat_assume(self.h, ipasir(*l)) } < 0 { return Err(self.err()); }
+        }
+        self.solve()
+    }
+    fn core(&mut self) -> anyhow::Result<Vec<Lit>> {
+        let mut n = 0u64;
+        if unsafe { mi355sat_core(self.h, std::ptr::null_mut(), 0, &mut n) } < 0 { return Err(self.err()); }
+        let mut out = vec![0i32; n as usize];
+        if unsafe { mi355sat_core(self.h, out.as_mut_ptr(), n, &mut n) } < 0 { return Err(self.err()); }
+        Ok(out.into_iter().map(|l| !from_ipasir(l)).collect())
     }
 }
 

@@ -2607,3 +2607,124 @@ __global__ __launch_bounds__(MS_WAVE) void ms_probe_kernel(MsShared sh, MsLayout
     if (w.status == MS_ST_RUNNING) w.status = confl ? MS_ST_UNSAT : MS_ST_SAT;
     wk_store<LV>(w, sh, L, __builtin_readcyclecounter() - t0);
 }
+
+// ---- final conflict analysis (MiniSat's analyzeFinal) ------------------------------------
+// Which assumptions a refutation rests on.  One workgroup (one wave) per worker that came back MS_ST_REFUTED; the
+// worker's slab is only READ (between two slices: the host may hand the worker a new cube right afterwards).
+// The assumption at index f = n_levels is false; level l <= n_assumps was opened by assumption l-1 (a dummy level,
+// without trail entry, for one that was already true).  var(assumps[f]) is marked, then the trail is walked down from
+// trail_n-1 to trail_lim[0], 64 entries per round (lane i holds position chunk_hi - i): a marked decision adds its
+// level's index to the core, a marked implied literal marks the variables of its reason.  Reasons point backwards on
+// the trail, so what a round marks inside the chunk is found by the next round; marks stay until the walk ends and a
+// lane's `done` flag keeps its literal from being expanded twice.  Level-0 variables sit below trail_lim[0] and are
+// never visited, so their marks are harmless.  Marks: one bit per variable of this kernel's own (not MsVarRec.seen), in
+// dynamic LDS (LM) or in the block's row of `scratch` (n_vars too large for LDS, or opts.lds_val = -1).
+// out: one row of out_words words per block, bit i = assumption index i; ok[b] = 0 if the slab contradicts the scheme
+// above (a decision that is not its level's assumption), which the host reports as an internal error.
+template <bool LM>
+__global__ __launch_bounds__(MS_WAVE) void ms_final_kernel(MsShared sh, MsLayout L, const char* slabs, const int32_t* workers,
+                                                          uint32_t* scratch, uint32_t* out, uint32_t out_words, int32_t* ok) {
+    HIP_DYNAMIC_SHARED(uint32_t, s_fmarks)
+    const int lane = (int)threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint32_t mwords = (sh.n_vars + 31) >> 5;
+    Gp<const char> slab = (Gp<const char>)(slabs + (size_t)workers[b] * L.slab_bytes);
+    Gp<const MsState> st = (Gp<const MsState>)(slab + L.state);
+    Gp<const int32_t> assumps = (Gp<const int32_t>)(slab + L.assumps);
+    Gp<const int32_t> trail = (Gp<const int32_t>)(slab + L.trail);
+    Gp<const MsVarRec> vrec = (Gp<const MsVarRec>)(slab + L.vrec);
+    Gp<uint32_t> row = (Gp<uint32_t>)out + (size_t)b * out_words;
+    LdsU32 lmarks = (LdsU32)s_fmarks;
+    Gp<uint32_t> gmarks = LM ? (Gp<uint32_t>)nullptr : (Gp<uint32_t>)scratch + (size_t)b * mwords;
+    for (uint32_t i = (uint32_t)lane; i < mwords; i += MS_WAVE) {
+        if (LM) lmarks[i] = 0;
+        else gmarks[i] = 0;
+    }
+    for (uint32_t i = (uint32_t)lane; i < out_words; i += MS_WAVE) row[i] = 0;
+    auto sync = [&]() {    // the wave's own marks and stores are visible to its next loads
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+        if (LM) lds_fence();
+    };
+    sync();
+    auto marked = [&](int v) -> bool {
+        const uint32_t x = LM ? lmarks[v >> 5] : __hip_atomic_load(&gmarks[v >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return (x >> (v & 31)) & 1u;
+    };
+    auto mark = [&](int v) {
+        if ((uint32_t)v >= sh.n_vars) return;
+        if (LM) lds_or(&lmarks[v >> 5], 1u << (v & 31));
+        else (void)__hip_atomic_fetch_or(&gmarks[v >> 5], 1u << (v & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto add_index = [&](int i) { (void)__hip_atomic_fetch_or(&row[i >> 5], 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const int n_levels = uni(st->n_levels), trail_n = uni(st->trail_n), n_a = uni(st->n_assumps);
+    const int f = n_levels;
+    const int cap = (int)(out_words * 32u);
+    bool bad = f < 0 || f >= n_a || f >= cap || trail_n < 0 || trail_n > (int)sh.n_vars || (uint32_t)n_a > L.assump_cap;
+    if (!bad) {
+        if (lane == 0) { add_index(f); mark(assumps[f] >> 1); }
+        const int lo = n_levels > 0 ? uni(((Gp<const int32_t>)(slab + L.trail_lim))[0]) : trail_n;
+        if (lo < 0) bad = true;
+        for (int hi = trail_n - 1; !bad && hi >= lo; hi -= MS_WAVE) {
+            const int pos = hi - lane;
+            const bool in = pos >= lo;
+            const int lit = in ? trail[pos] : 0;
+            const int v = lit >> 1;
+            bool done = false, err = in && (uint32_t)v >= sh.n_vars;
+            for (;;) {
+                sync();     // this round's marks are seen by the next
+                const bool mine = in && !err && !done && marked(v);
+                if (ballot(mine) == 0) break;
+                int nl = 0, r = 0, size = 0;
+                uint32_t start = 0;
+                int4 l0 = make_int4(0, 0, 0, 0), l1 = make_int4(0, 0, 0, 0);
+                if (mine) {
+                    done = true;
+                    const MsVarRec rec = vrec[v];
+                    r = rec.reason;
+                    size = (int)rec.size;
+                    start = rec.start;
+                    if (r == MS_REASON_NONE) {                  // a decision: the assumption that opened its level
+                        if (rec.level < 1 || rec.level > n_levels || assumps[rec.level - 1] != lit) err = true;
+                        else add_index(rec.level - 1);
+                    } else if (MS_IS_TERN_REASON(r)) {
+                        const int e = MS_TERN_REASON_ENTRY(r);
+                        const ms_int2 tp = ((Gp<const ms_int2>)sh.tern_pairs)[e];
+                        l0 = make_int4(((Gp<const int32_t>)sh.tern_owner)[e], tp.x, tp.y, 0);
+                        nl = 3;
+                    } else if (MS_IS_BIN_REASON(r)) {
+                        l0.x = MS_BIN_REASON_LIT(r);
+                        nl = 1;
+                    } else if (size > 0 && size <= 8) {
+                        Gp<const int32_t> cl = ((uint32_t)r < sh.n_orig ? (Gp<const int32_t>)sh.cl_lits : (Gp<const int32_t>)(slab + L.lc_lits)) + start;
+                        l0 = *(Gp<const int4>)cl;
+                        if (size > 4) l1 = *(Gp<const int4>)(cl + 4);
+                        nl = size;
+                    }
+                }
+                for (int j = 0; j < nl; j++) {    // (own variable included: it is marked already)
+                    const int q = j < 4 ? (j == 0 ? l0.x : (j == 1 ? l0.y : (j == 2 ? l0.z : l0.w)))
+                                        : (j == 4 ? l1.x : (j == 5 ? l1.y : (j == 6 ? l1.z : l1.w)));
+                    mark(q >> 1);
+                }
+                // long reasons (> 8 literals, or the range not in the record): the whole wave, 64 literals per round
+                for (u64 bm = ballot(mine && r >= 0 && !(size > 0 && size <= 8)); bm != 0; bm &= bm - 1) {
+                    const int fb = first_lane(bm);
+                    const int cref = bcast(r, fb);
+                    int n = bcast(size, fb);
+                    uint32_t s0 = (uint32_t)bcast((int)start, fb);
+                    if (n == 0) {
+                        const MsClauseRec h = ((Gp<const MsClauseRec>)(slab + L.wl))[cref];
+                        n = (int)uni((int)h.size);
+                        s0 = (uint32_t)uni((int)h.start);
+                    }
+                    Gp<const int32_t> cl = ((uint32_t)cref < sh.n_orig ? (Gp<const int32_t>)sh.cl_lits : (Gp<const int32_t>)(slab + L.lc_lits)) + s0;
+                    for (int k = lane; k - lane < n; k += MS_WAVE)
+                        if (k < n) mark(cl[k] >> 1);
+                }
+            }
+            if (ballot(err)) bad = true;
+        }
+    }
+    sync();
+    if (lane == 0) ok[b] = bad ? 0 : 1;
+}

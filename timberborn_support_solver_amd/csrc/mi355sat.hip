@@ -376,6 +376,13 @@ struct mi355sat {
     std::vector<MsElim> elims;                 // variables eliminated before search and the clauses that rebuild their values
     std::vector<int32_t> elim_lits;
     struct SweepHolder* sweep = nullptr;        // stepwise sweep in progress (mi355sat_sweep_*)
+    // IPASIR assumptions (mi355sat_assume) of the next solve(), and the failed-assumption cores: caller's literals, in the
+    // order of the caller's assumption list
+    std::vector<int32_t> assumps;
+    std::vector<int32_t> core;                 // of the last solve(), valid after UNSAT until the next add / assume / solve
+    bool core_valid = false;
+    std::vector<std::vector<int32_t>> batch_cores;   // of the last solve_batch(), per instance
+    std::vector<uint8_t> batch_core_valid;
 };
 
 namespace {
@@ -1511,9 +1518,14 @@ void proof_drain(mi355sat& s) {
     }
     if (any) { HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * W, s.stream)); HIPCHK(hipStreamSynchronize(s.stream)); }
 }
-void proof_close(mi355sat& s, bool unsat) {
+// An UNSAT answer ends the proof with the clause of the negated core: under assumptions, what the formula implies about
+// them; without any (or when the formula itself is refuted), the empty clause.
+void proof_close(mi355sat& s, bool unsat, const std::vector<int32_t>& core = {}) {
     if (!s.proof_file) return;
-    if (unsat) fputs("0\n", s.proof_file);
+    if (unsat) {
+        for (int32_t l : core) fprintf(s.proof_file, "%d ", -l);
+        fputs("0\n", s.proof_file);
+    }
     fclose(s.proof_file);
     s.proof_file = nullptr;
 }
@@ -1555,6 +1567,13 @@ struct Sweep {
     std::vector<uint32_t> open;                  // open cubes per instance
     uint64_t n_splits = 0, n_closed = 0;
     DevBuf<int32_t> d_upd, d_data;
+    // failed-assumption cores (solve() and solve_batch() only; the public sweep API launches nothing for them): per
+    // instance, one flag per entry of the caller's assumption list
+    bool cores = false;
+    std::vector<uint32_t> base_src;              // per entry of base_assump: its index in the caller's list of the instance
+    std::vector<std::vector<uint8_t>> core_flag;
+    DevBuf<int32_t> d_fw, d_fok;
+    DevBuf<uint32_t> d_fout, d_fscratch;
 };
 
 int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
@@ -1590,6 +1609,8 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     sw.dropped.assign(n_instances, 0);
     sw.n_moved = 0;
     sw.ramp_ms = 0;
+    sw.core_flag.assign(sw.cores ? n_instances : 0, {});
+    for (size_t i = 0; i < sw.core_flag.size(); i++) sw.core_flag[i].assign(assump_off[i + 1] - assump_off[i], 0);
     if (P.unsat) {
         std::fill(sw.results.begin(), sw.results.end(), MI355SAT_UNSAT);
         sw.decided = n_instances;
@@ -1606,17 +1627,31 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     s.d_proof_len.release();
     s.proof_cap = 0;
     sw.split = s.opts.cube_split > 0 && want > n_instances;   // opt-in: see DESIGN.md (measured: not yet a win)
-    std::vector<int32_t> a_int(assump.size());
-    for (size_t i = 0; i < assump.size(); i++) {
-        int32_t d = assump[i];
-        if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > P.n_vars) throw HipErr{"assumption literal out of range"};
-        int32_t l = to_internal(d);
-        while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);     // a variable replaced by an equivalent literal
-        a_int[i] = 2 * (int32_t)P.perm[l >> 1] | (l & 1);
+    // device literals, each at most once per instance (a repeated assumption would open a level of its own: a list longer
+    // than n_vars would overrun trail_lim); base_src keeps where each one came from in the caller's list
+    std::vector<int32_t> a_int;
+    std::vector<uint64_t> a_off{0};
+    sw.base_src.clear();
+    {
+        std::vector<uint32_t> stamp(2 * (size_t)P.n_vars, 0);
+        for (uint32_t i = 0; i < n_instances; i++) {
+            for (uint64_t k = assump_off[i]; k < assump_off[i + 1]; k++) {
+                int32_t d = assump[k];
+                if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > P.n_vars) throw HipErr{"assumption literal out of range"};
+                int32_t l = to_internal(d);
+                while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);     // a variable replaced by an equivalent literal
+                l = 2 * (int32_t)P.perm[l >> 1] | (l & 1);
+                if (stamp[l] == i + 1) continue;
+                stamp[l] = i + 1;
+                a_int.push_back(l);
+                sw.base_src.push_back((uint32_t)(k - assump_off[i]));
+            }
+            a_off.push_back(a_int.size());
+        }
     }
     uint32_t max_assumps = 0;
     for (uint32_t i = 0; i < n_instances; i++)
-        max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)(assump_off[i + 1] - assump_off[i]));
+        max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)(a_off[i + 1] - a_off[i]));
     const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps;
     const uint32_t initial = (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) ? std::max(256u, n_instances) / n_instances * n_instances : 0;
     upload_formula(s, P, assump_cap, 0, want, initial);
@@ -1632,12 +1667,12 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * s.n_workers, s.stream));
     }
     reset_workers(s);
-    customize(s, &a_int, &assump_off, nullptr, nullptr, n_instances, sw.split ? (int32_t)n_instances : -1);
+    customize(s, &a_int, &a_off, nullptr, nullptr, n_instances, sw.split ? (int32_t)n_instances : -1);
     HIPCHK(hipStreamSynchronize(s.stream));
     const uint32_t W = s.n_workers;
     s.stats.workers = W;
     sw.base_assump = a_int;
-    sw.base_off = assump_off;
+    sw.base_off = a_off;
     sw.w_inst.assign(W, 0);
     sw.w_cube.assign(W, {});
     sw.w_busy.assign(W, 0);
@@ -1648,7 +1683,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         sw.w_inst[w] = (int32_t)inst;
         if (!sw.split || w < n_instances) {
             sw.w_busy[w] = 1;
-            sw.w_cube[w].assign(a_int.begin() + assump_off[inst], a_int.begin() + assump_off[inst + 1]);
+            sw.w_cube[w].assign(a_int.begin() + a_off[inst], a_int.begin() + a_off[inst + 1]);
             sw.open[inst]++;
         }
     }
@@ -1800,6 +1835,43 @@ void rebalance_workers(mi355sat& s, Sweep& sw) {
     HIPCHK(hipStreamSynchronize(s.stream));
 }
 
+// Failed assumptions of the workers in fw, which came back MS_ST_REFUTED from the slice just gathered: ms_final_kernel,
+// on the stream ahead of anything that rewrites a slab's assumptions (rebalance_workers, schedule_cubes, customize).  The
+// kernel reports indices into the worker's (deduplicated) assumption list: those below its instance's own count map back
+// to the caller's list through base_src; split literals (cube_split) drop out - the cubes of an instance are the leaves
+// of a complete split tree, so the union of their cores restricted to the instance's assumptions is a core of it.
+int final_cores(mi355sat& s, Sweep& sw, const std::vector<int32_t>& fw) {
+    const uint32_t n = (uint32_t)fw.size();
+    const uint32_t out_words = std::max<uint32_t>(1, (s.L.assump_cap + 31) / 32);
+    const uint32_t mwords = (s.n_vars + 31) / 32;
+    const bool lds = s.opts.lds_val >= 0 && 4ull * mwords <= 48 * 1024;   // the marks in LDS, or a scratch row per workgroup
+    sw.d_fw.upload(fw, s.stream);
+    if (sw.d_fout.n < (size_t)n * out_words) sw.d_fout.alloc((size_t)n * out_words);
+    if (sw.d_fok.n < n) sw.d_fok.alloc(n);
+    if (lds) {
+        hipLaunchKernelGGL(ms_final_kernel<true>, dim3(n), dim3(MS_WAVE), 4 * mwords, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
+                           (const int32_t*)sw.d_fw.p, (uint32_t*)nullptr, sw.d_fout.p, out_words, sw.d_fok.p);
+    } else {
+        if (sw.d_fscratch.n < (size_t)n * std::max<uint32_t>(mwords, 1)) sw.d_fscratch.alloc((size_t)n * std::max<uint32_t>(mwords, 1));
+        hipLaunchKernelGGL(ms_final_kernel<false>, dim3(n), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
+                           (const int32_t*)sw.d_fw.p, sw.d_fscratch.p, sw.d_fout.p, out_words, sw.d_fok.p);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> out((size_t)n * out_words);
+    std::vector<int32_t> ok(n);
+    HIPCHK(hipMemcpyAsync(out.data(), sw.d_fout.p, sizeof(uint32_t) * out.size(), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(ok.data(), sw.d_fok.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    for (uint32_t k = 0; k < n; k++) {
+        if (!ok[k]) { set_error(&s, "device solver internal error (final conflict analysis)"); return MI355SAT_ERR_STATE; }
+        const uint32_t inst = (uint32_t)sw.w_inst[fw[k]];
+        const uint64_t b0 = sw.base_off[inst], nb = sw.base_off[inst + 1] - b0;
+        for (uint64_t i = 0; i < nb; i++)
+            if ((out[(size_t)k * out_words + i / 32] >> (i % 32)) & 1u) sw.core_flag[inst][sw.base_src[b0 + i]] = 1;
+    }
+    return 0;
+}
+
 // One slice of the search kernel over all workers.  Returns 0 or a negative error.
 int sweep_step(mi355sat& s, Sweep& sw) {
     if (!sw.active) return 0;
@@ -1833,6 +1905,7 @@ int sweep_step(mi355sat& s, Sweep& sw) {
     gather_states(s, sw.sts);
     int rc = 0;
     uint64_t confl = 0;
+    std::vector<int32_t> fw;     // refuted workers whose failed assumptions are wanted (final_cores)
     for (uint32_t w = 0; w < s.n_workers; w++) {
         const MsState& st = sw.sts[w];
         confl += st.conflicts;
@@ -1849,10 +1922,15 @@ int sweep_step(mi355sat& s, Sweep& sw) {
         }
         if (st.status == MS_ST_UNSAT) {   // refuted without any decision: the formula itself, whatever the assumptions
             for (uint32_t i = 0; i < n_instances; i++)
-                if (inst_open(sw, i)) { sw.results[i] = MI355SAT_UNSAT; sw.winner[i] = (int32_t)w; sw.decided++; }
+                if (inst_open(sw, i)) {
+                    sw.results[i] = MI355SAT_UNSAT; sw.winner[i] = (int32_t)w; sw.decided++;
+                    if (sw.cores) std::fill(sw.core_flag[i].begin(), sw.core_flag[i].end(), 0);   // the empty core
+                }
             continue;
         }
         if (!inst_open(sw, inst)) continue;
+        // with splitting every closed cube contributes to its instance's core, without it the deciding worker alone
+        if (sw.cores && st.status == MS_ST_REFUTED) fw.push_back((int32_t)w);
         if (st.status == MS_ST_SAT) { sw.results[inst] = MI355SAT_SAT; sw.winner[inst] = (int32_t)w; sw.decided++; }
         else if (st.status == MS_ST_UNSAT || (st.status == MS_ST_REFUTED && (!sw.split || sw.open[inst] == 0))) {
             // the formula itself refuted, or (with splitting) the last open cube of the instance closed;
@@ -1872,6 +1950,7 @@ int sweep_step(mi355sat& s, Sweep& sw) {
                 (unsigned long long)nl);
     }
     if (rc) return rc;
+    if (!fw.empty() && (rc = final_cores(s, sw, fw)) != 0) return rc;   // before any slab's assumptions are rewritten below
     HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
     if (sw.decided == n_instances || (sw.stop_at_first && sw.decided > 0)) return 0;
     if (sw.split) schedule_cubes(s, sw);
@@ -1900,14 +1979,26 @@ void sweep_end(mi355sat& s, Sweep& sw) {
     consume_interrupt(s);
 }
 
+// cores (may be null): per instance, the caller's assumptions its UNSAT answer rests on, in the caller's order (empty
+// for the other answers)
 int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
-               uint32_t n_instances, std::vector<int32_t>& results, std::vector<int32_t>& winner, bool stop_at_first) {
+               uint32_t n_instances, std::vector<int32_t>& results, std::vector<int32_t>& winner, bool stop_at_first,
+               std::vector<std::vector<int32_t>>* cores = nullptr) {
     Sweep sw;
+    sw.cores = cores != nullptr;
     int rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first);
     while (!rc && !sweep_finished(s, sw)) rc = sweep_step(s, sw);
     sweep_end(s, sw);
     results = sw.results;
     winner = sw.winner;
+    if (cores) {
+        cores->assign(n_instances, {});
+        for (uint32_t i = 0; i < n_instances && !rc; i++) {
+            if (results[i] != MI355SAT_UNSAT) continue;
+            for (uint64_t k = 0; k < sw.core_flag[i].size(); k++)
+                if (sw.core_flag[i][k]) (*cores)[i].push_back(assump[assump_off[i] + k]);
+        }
+    }
     return rc;
 }
 
@@ -2010,6 +2101,7 @@ static int add_clause_impl(mi355sat* s, const int32_t* l, uint64_t n) {
     }
     s->lits.insert(s->lits.end(), l, l + n);
     s->offs.push_back(s->lits.size());
+    s->core_valid = false;     // IPASIR: adding leaves the UNSAT state
     s->stats.n_clauses++;
     s->stats.max_var = s->max_var;
     s->stats.avg_clause_len = (double)s->lits.size() / (double)s->stats.n_clauses;
@@ -2044,6 +2136,47 @@ void mi355sat_interrupt(mi355sat* s) {
     if (s->stop_flag) __atomic_store_n(s->stop_flag, 1, __ATOMIC_SEQ_CST);
 }
 
+int mi355sat_assume(mi355sat* s, int32_t lit) {
+    if (!s) return MI355SAT_ERR_ARG;
+    const uint64_t v = (uint64_t)(lit < 0 ? -(int64_t)lit : lit);
+    if (lit == 0 || v > MS_MAX_VARS) { s->err = "assumption literal out of range"; return MI355SAT_ERR_ARG; }
+    try {
+        s->assumps.push_back(lit);
+    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    if (v > s->max_var) { s->max_var = v; s->stats.max_var = v; }   // as mi355sat_reserve
+    s->core_valid = false;
+    return 0;
+}
+
+int mi355sat_failed(mi355sat* s, int32_t lit) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (!s->core_valid) { s->err = "no failed assumptions: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    return std::find(s->core.begin(), s->core.end(), lit) != s->core.end() ? 1 : 0;
+}
+
+static int copy_core(mi355sat* s, const std::vector<int32_t>& core, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = core.size();
+    if (!out) return 0;
+    if (cap < core.size()) { s->err = "core buffer too small"; return MI355SAT_ERR_ARG; }
+    std::copy(core.begin(), core.end(), out);
+    return 0;
+}
+
+int mi355sat_core(mi355sat* s, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (!s->core_valid) { s->err = "no core: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    return copy_core(s, s->core, out, cap, n);
+}
+
+int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (instance >= s->batch_core_valid.size() || !s->batch_core_valid[instance]) {
+        s->err = "no core: instance out of range or not UNSAT in the last solve_batch()";
+        return instance >= s->batch_core_valid.size() && !s->batch_core_valid.empty() ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
+    }
+    return copy_core(s, s->batch_cores[instance], out, cap, n);
+}
+
 int mi355sat_set_proof_path(mi355sat* s, const char* path) {
     if (!s) return MI355SAT_ERR_ARG;
     s->proof_path = path ? path : "";
@@ -2052,18 +2185,23 @@ int mi355sat_set_proof_path(mi355sat* s, const char* path) {
 
 int mi355sat_solve(mi355sat* s) {
     if (!s) return MI355SAT_ERR_ARG;
+    std::vector<int32_t> assump;
+    assump.swap(s->assumps);     // IPASIR: the assumptions hold for this solve only, whatever it returns
+    s->core.clear();
+    s->core_valid = false;
     if (!s->pending.empty()) { s->err = "solve() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
     const double t0 = now_s();
     int result;
     try {
         HIPCHK(hipSetDevice(s->device));
-        std::vector<int32_t> assump;
-        std::vector<uint64_t> aoff{0, 0};
+        std::vector<uint64_t> aoff{0, (uint64_t)assump.size()};
         std::vector<int32_t> results, winner;
-        int rc = run_search(*s, assump, aoff, 1, results, winner, true);
+        std::vector<std::vector<int32_t>> cores;
+        int rc = run_search(*s, assump, aoff, 1, results, winner, true, &cores);
         if (rc) { proof_close(*s, false); s->stats.solve_seconds += now_s() - t0; return rc; }   // (a truncated proof file is closed, not leaked)
         result = results[0];
-        proof_close(*s, result == MI355SAT_UNSAT);
+        if (result == MI355SAT_UNSAT) { s->core = cores[0]; s->core_valid = true; }
+        proof_close(*s, result == MI355SAT_UNSAT, s->core);
         s->model.clear();
         if (result == MI355SAT_SAT) fetch_model(*s, (uint32_t)winner[0], s->model, s->max_var);
     } catch (HipErr& he) {
@@ -2093,11 +2231,17 @@ int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* as
         std::vector<int32_t> assump;
         if (aoff.back()) assump.assign(assumps + assump_offsets[0], assumps + assump_offsets[n_instances]);
         std::vector<int32_t> results, winner;
-        int rc = run_search(*s, assump, aoff, (uint32_t)n_instances, results, winner, stop_at_first != 0);
+        s->batch_cores.clear();
+        s->batch_core_valid.clear();
+        std::vector<std::vector<int32_t>> cores;
+        int rc = run_search(*s, assump, aoff, (uint32_t)n_instances, results, winner, stop_at_first != 0, &cores);
         if (rc) { s->stats.solve_seconds += now_s() - t0; return rc; }
         s->batch_models.assign(n_instances, {});
+        s->batch_cores.swap(cores);
+        s->batch_core_valid.assign(n_instances, 0);
         for (uint64_t i = 0; i < n_instances; i++) {
             results_out[i] = results[i];
+            s->batch_core_valid[i] = results[i] == MI355SAT_UNSAT;
             if (results[i] == MI355SAT_SAT && winner[i] >= 0) fetch_model(*s, (uint32_t)winner[i], s->batch_models[i], s->max_var);
             if (results[i] == MI355SAT_SAT) s->stats.n_sat++;
             else if (results[i] == MI355SAT_UNSAT) s->stats.n_unsat++;

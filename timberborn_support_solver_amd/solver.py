@@ -82,6 +82,10 @@ def _bind(L):
     L.mi355sat_add.argtypes = [vp, ctypes.c_int32]
     L.mi355sat_reserve.argtypes = [vp, ctypes.c_uint64]
     L.mi355sat_solve.argtypes = [vp]
+    L.mi355sat_assume.argtypes = [vp, ctypes.c_int32]
+    L.mi355sat_failed.argtypes = [vp, ctypes.c_int32]
+    L.mi355sat_core.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_core_of.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_solve_batch.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_int]
     L.mi355sat_sweep_begin.argtypes = [vp, vp, vp, ctypes.c_uint64]
     L.mi355sat_sweep_step.argtypes = [vp, vp, vp]
@@ -154,7 +158,9 @@ class Mi355Sat:
 
     def _check(self, rc, what):
         if rc < 0:
-            raise SolverError(f"{what} failed ({rc}): " + (self._L.mi355sat_last_error(self._h) or b"").decode())
+            e = SolverError(f"{what} failed ({rc}): " + (self._L.mi355sat_last_error(self._h) or b"").decode())
+            e.code = rc     # the MI355SAT_ERR_* value
+            raise e
         return rc
 
     @staticmethod
@@ -182,8 +188,37 @@ class Mi355Sat:
     def interrupter(self):
         return Interrupter(self._L, self._ref, self._lock)
 
-    def solve(self):
+    def solve(self, assumptions=()):
+        """Solve (rustsat `solve`), or under DIMACS assumption literals that hold for this call only (`solve_assumps`)."""
+        for l in assumptions:
+            self.assume(l)
         return SolverResult(self._check(self._L.mi355sat_solve(self._h), "solve"))
+
+    # ---- SolveIncremental (IPASIR assume / failed)
+    def assume(self, lit):
+        """Assumption for the next solve() only."""
+        self._check(self._L.mi355sat_assume(self._h, int(lit)), "assume")
+        self._n_vars = max(self._n_vars, abs(int(lit)))
+
+    def failed(self, lit):
+        """After solve() returned Unsat: whether assumption `lit` is in the core."""
+        return self._check(self._L.mi355sat_failed(self._h, int(lit)), "failed") == 1
+
+    def _core(self, fn, *args):
+        n = ctypes.c_uint64(0)
+        self._check(fn(self._h, *args, None, 0, ctypes.byref(n)), "core")
+        out = np.zeros(n.value, dtype=np.int32)
+        self._check(fn(self._h, *args, _p(out), n.value, ctypes.byref(n)), "core")
+        return [int(l) for l in out[:n.value]]
+
+    def core(self):
+        """After solve() returned Unsat: the assumptions (DIMACS literals, in the order given) the refutation rests on;
+        formula AND core is UNSAT.  Raises SolverError in any other state."""
+        return self._core(self._L.mi355sat_core)
+
+    def core_of(self, instance):
+        """The same for an Unsat instance of the last solve_batch()."""
+        return self._core(self._L.mi355sat_core_of, instance)
 
     def solve_batch(self, assumption_sets, stop_at_first=False):
         """assumption_sets: list of lists of DIMACS literals.  Returns [SolverResult]."""
