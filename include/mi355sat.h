@@ -280,6 +280,28 @@ int mi355sat_stats(const mi355sat* s, mi355sat_stats_t* out);
  * too small. */
 int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_t* n_records);
 
+/* Test hooks: which build of the search kernel a launch runs.  ms_search_kernel<LV, WPS> exists in six builds (assignment
+ * staged in LDS or left in the worker's slab; compiled for 1, 2 or 4 waves per SIMD) and every launch picks one from the
+ * number of workers it runs, opts.one_per_simd, opts.lds_val and an LDS budget (150 KB per CU shared by the launch's
+ * workers per CU, minus a workgroup's static LDS, at most 64 KB).  tests/ force each build and assert here that it ran. */
+typedef struct mi355sat_search_build {
+    int32_t  lds;              /* 1 = assignment and marks in LDS, 0 = in the slab */
+    int32_t  wps;              /* waves per SIMD the build was compiled for: 1, 2 or 4 (0: not a search launch) */
+    uint32_t dyn_lds_bytes;    /* dynamic LDS per workgroup of the launch (0 unless lds) */
+    uint32_t active;           /* workers (workgroups of one wavefront) the launch ran */
+    uint32_t lds_val_bytes;    /* what staging this formula's assignment and marks takes */
+    uint32_t builds_seen;      /* bit (3 * lds + {wps 1: 0, 2: 1, 4: 2}) set for every build the handle has launched so far */
+    uint64_t launches;         /* search launches of the handle so far */
+} mi355sat_search_build;
+/* The build of the handle's last search launch; MI355SAT_ERR_STATE before the first one. */
+int mi355sat_debug_last_search_build(const mi355sat* s, mi355sat_search_build* out);
+/* The selection rule alone, nothing is launched (no handle, no device): what a launch of `active` >= 1 workers would run for
+ * a formula of lds_val_bytes under opts.lds_val / opts.one_per_simd.  mode 0 = search (else BCP / probing: wps 0).  staged =
+ * the handle's own LDS decision for the kernels without a budget rule (1 / 0), or -1 to derive it as a solve does.
+ * builds_seen and launches stay 0. */
+int mi355sat_debug_search_build_rule(uint32_t active, uint32_t lds_val_bytes, int32_t staged, int32_t lds_val,
+                                     int32_t one_per_simd, int32_t mode, mi355sat_search_build* out);
+
 /* Clause exchange BETWEEN handles that search the SAME formula - the replicas of the sharded loop's last bounds, one
  * handle per GPU (every rank poses the reference's next bound, crates/repl/src/main.rs:292-295, with its own
  * seed).  Inside one handle the workers pass their short / low-LBD learnt clauses on through a ring on the device;

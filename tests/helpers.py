@@ -129,6 +129,14 @@ def assert_ring_records_are_implied(solver, cnf, max_records=None):
     return len(recs)
 
 
+def assert_search_build(solver, lds, wps):
+    """The handle's search launches all ran ms_search_kernel<lds, wps> (mi355sat_debug_last_search_build): the last one
+    did, and no other build was launched since the handle was made.  Returns the hook's record."""
+    b = solver.debug_last_search_build()
+    assert (b["lds"], b["wps"]) == (lds, wps) and b["builds"] == {(lds, wps)} and b["launches"] > 0, (b, "wanted", (lds, wps))
+    return b
+
+
 def long_list_formula(seed, n_vars=360, n_long=140, n_hubs=6, per_hub=44, hub_len=(9, 40)):
     """A formula cut for the BCP step's side paths: clauses of 10..48 literals (tails to scan, several per step), a few
     hub literals watched by 44 long clauses each (watch lists far longer than a lane group: the flat remainder, its

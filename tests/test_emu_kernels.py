@@ -8,7 +8,7 @@ import time
 import numpy as np
 import pytest
 
-from helpers import (assert_ring_records_are_implied, VERDICTS, check_sat_answer, emu_lib, long_list_formula, make_grid, platform_defs,
+from helpers import (assert_ring_records_are_implied, assert_search_build, VERDICTS, check_sat_answer, emu_lib, long_list_formula, make_grid, platform_defs,
                      scripted_decisions)
 from oracle import oracle as ora
 from timberborn_support_solver_amd import Encoding, Mi355Sat, PlatformLimits, SolverResult, solver_loop
@@ -571,21 +571,88 @@ def test_emulated_reopened_bound_without_weights_gets_a_worker():
     s.close()
 
 
-@pytest.mark.parametrize("one_per_simd", [2, 4], ids=["two-waves-build", "full-fleet-build"])
-def test_emulated_called_builds_of_the_search_kernel(one_per_simd):
-    """The search kernel exists in three builds (waves per SIMD 1 / 2 / 4).  Small fleets run the inlined one; this forces
-    the two CALLED builds - the per-conflict code a function that works on register copies (2) or on the caller's context
-    (4) - through the same verdict / model / exchange checks."""
-    for terrain, pset, k, want in [("ex1", "1x1", 2, "Unsat"), ("ex1", "1x1", 3, "Sat"), ("rect8x8", "1x1", 3, "Unsat")]:
+# The six builds of ms_search_kernel<LV, WPS>: opts.one_per_simd 0 / 2 / 4 gives a fleet of four workers the 1- / 2- /
+# 4-waves-per-SIMD build, opts.lds_val 1 / -1 the assignment in LDS / in the slab.  assert_search_build proves which one ran.
+BUILDS = pytest.mark.parametrize("one_per_simd,lds_val", [(o, l) for o in (0, 2, 4) for l in (1, -1)],
+                                 ids=[f"{w}-{a}" for w in ("one-wave-build", "two-waves-build", "full-fleet-build") for a in ("lds", "slab")])
+
+
+def wanted_build(one_per_simd, lds_val):
+    return (1 if lds_val == 1 else 0, max(1, one_per_simd))
+
+
+@BUILDS
+def test_emulated_called_builds_of_the_search_kernel(tmp_path, one_per_simd, lds_val):
+    """The search kernel exists in three builds (waves per SIMD 1 / 2 / 4), each with the assignment in LDS or in the slab.
+    Small fleets run the inlined one and small formulas stage the assignment in LDS; this forces every one of the six - the
+    CALLED builds have the per-conflict code as a function that works on register copies (2) or on the caller's context (4,
+    which also has no sort buffer, no recursive minimisation, no vivification and keeps its marks as bytes) - through the same
+    checks: the hook names the build that ran, golden verdict, model, counters, a RUP-checked DRUP proof and an exchange
+    ring that holds only consequences of the formula."""
+    from timberborn_support_solver_amd.dimacs import read_drup
+    for terrain, pset, k, want in [("ex1", "1x1", 2, "Unsat"), ("ex1", "1x1", 3, "Sat"), ("rect8x8", "1x1", 3, "Unsat"),
+                                   ("rect8x8", "default", 1, "Unsat"), ("rect8x8", "default", 2, "Sat")]:
+        v = [x for x in VERDICTS["verdicts"] if (x["terrain"], x["platforms"], x["k"]) == (terrain, pset, k)][0]
+        assert v["verdict"] == want.upper()
         grid = make_grid(terrain)
         enc = Encoding.encode(platform_defs(pset), grid)
         cnf = enc.with_limits_into_cnf(PlatformLimits({(1, 1): k}))
-        s = emu_solver(workers=4, slice_conflicts=10, one_per_simd=one_per_simd)
+        proof = str(tmp_path / f"{terrain}-{pset}-{k}.drup")
+        s = emu_solver(workers=4, slice_conflicts=10, one_per_simd=one_per_simd, lds_val=lds_val)
+        if want == "Unsat":
+            s.set_proof_path(proof)
         s.add_cnf(cnf.lits, cnf.offsets)
         assert s.solve().name == want
+        b = assert_search_build(s, *wanted_build(one_per_simd, lds_val))
+        assert b["active"] == 4 and b["dyn_lds_bytes"] == (b["lds_val_bytes"] if lds_val == 1 else 0)
+        st = s.stats()
+        assert st["propagations"] == st["n_deq"] and st["n_sat"] + st["n_unsat"] == 1
         if want == "Sat":
             check_sat_answer(cnf, s.full_solution(cnf.n_vars), enc, grid, k)
+        else:
+            assert ora.check_rup(cnf.lits, cnf.offsets, cnf.n_vars, read_drup(proof)) == 1, (terrain, pset, k)
+            assert assert_ring_records_are_implied(s, cnf) > 0, (terrain, pset, k)      # the exchange ran in this build
         s.close()
+
+
+@BUILDS
+def test_emulated_builds_sweep_under_assumptions_and_reduce_db(one_per_simd, lds_val):
+    """test_emulated_sweep_under_assumptions_and_reduce_db in every build: a batch under assumptions with a clause
+    database small enough to be reduced (and the dropped clauses deleted) while it runs."""
+    grid = make_grid("rect8x8")
+    enc = Encoding.encode(platform_defs("1x1"), grid)
+    cnf = enc.with_limits_into_cnf(PlatformLimits({(1, 1): 8}), sweep=True)
+    ks = [3, 4, 8]
+    s = emu_solver(workers=3, slice_conflicts=100, reduce_first=25, reduce_inc=5, one_per_simd=one_per_simd, lds_val=lds_val)
+    s.add_cnf(cnf.lits, cnf.offsets)
+    res = s.solve_batch([[-int(cnf.card_outputs[k])] if k < 8 else [] for k in ks])
+    assert [r.name for r in res] == ["Unsat", "Sat", "Sat"]
+    assert_search_build(s, *wanted_build(one_per_simd, lds_val))
+    for i, k in enumerate(ks):
+        if res[i] == SolverResult.Sat:
+            check_sat_answer(cnf, s.solution_of(i, cnf.n_vars), enc, grid, k)
+    st = s.stats()
+    assert st["reduce_dbs"] > 0 and st["propagations"] == st["n_deq"]
+    s.close()
+
+
+@BUILDS
+def test_emulated_builds_repeat_themselves_in_deterministic_mode(one_per_simd, lds_val):
+    """opts.deterministic in every build: two runs with the same seed report equal counters."""
+    grid = make_grid("rect8x8")
+    enc = Encoding.encode(platform_defs("1x1"), grid)
+    cnf = enc.with_limits_into_cnf(PlatformLimits({(1, 1): 3}))
+    runs = []
+    for _ in range(2):
+        s = emu_solver(workers=4, slice_conflicts=25, deterministic=1, seed=7, one_per_simd=one_per_simd, lds_val=lds_val)
+        s.add_cnf(cnf.lits, cnf.offsets)
+        assert s.solve() == SolverResult.Unsat
+        assert_search_build(s, *wanted_build(one_per_simd, lds_val))
+        st = s.stats()
+        runs.append((st["conflicts"], st["propagations"], st["decisions"], st["restarts"], st["learnt_literals"], st["shared_exported"],
+                     st["shared_imported"]))
+        s.close()
+    assert runs[0] == runs[1] and runs[0][0] > 0 and runs[0][5] > 0, runs
 
 
 def test_emulated_deterministic_mode_repeats_itself():

@@ -1,6 +1,6 @@
 """Failed-assumption cores on the MI355X: ms_final_kernel after the real search kernel builds (one worker per SIMD,
 two and four waves per SIMD; assignment in LDS or in the slab, which also switches the final walk's marks between
-LDS and a scratch row), a 64-instance solve_batch, a DRUP proof under assumptions and the C replay of the Rust
+LDS and a scratch row; which build ran is asserted through mi355sat_debug_last_search_build), a 64-instance solve_batch, a DRUP proof under assumptions and the C replay of the Rust
 shim's SolveIncremental calls.  Every core is checked by the oracle."""
 import numpy as np
 import pytest
@@ -22,6 +22,17 @@ def cached_sweep_cnf(terrain, pset, k_max):
     return _cnfs[key]
 
 
+def assert_ran_the_build_asked_for(s, one_per_simd, lds_val):
+    """The default fleets of these formulas stay at or below 1024 workers, so one_per_simd = 0 / 2 / 4 means the 1- / 2- /
+    4-waves build in every launch; with lds_val = 0 the last launch's LDS choice is the selection rule's for its fleet."""
+    b = s.debug_last_search_build()
+    assert b["wps"] == max(1, one_per_simd) and {w for _, w in b["builds"]} == {b["wps"]} and b["active"] <= 1024, b
+    rule = Mi355Sat.debug_search_build_rule(b["active"], b["lds_val_bytes"], lds_val=lds_val, one_per_simd=one_per_simd)
+    assert (b["lds"], b["dyn_lds_bytes"]) == (rule["lds"], rule["dyn_lds_bytes"]), (b, rule)
+    if lds_val == -1:
+        assert b["lds"] == 0 and {l for l, _ in b["builds"]} == {0}
+
+
 @pytest.mark.parametrize("lds_val", [0, -1])
 @pytest.mark.parametrize("one_per_simd", [0, 2, 4])
 def test_cores_on_every_search_build(one_per_simd, lds_val):
@@ -32,6 +43,7 @@ def test_cores_on_every_search_build(one_per_simd, lds_val):
         s.add_cnf(cnf.lits, cnf.offsets)
         s.reserve(nv)
         assert s.solve(a) == SolverResult.Unsat, (terrain, k)
+        assert_ran_the_build_asked_for(s, one_per_simd, lds_val)
         core = s.core()
         assert core == [-int(cnf.card_outputs[k])], (terrain, k, core)
         assert_core(core, a, cnf, nv)
@@ -49,6 +61,7 @@ def test_cores_on_every_search_build(one_per_simd, lds_val):
     s = Mi355Sat(one_per_simd=one_per_simd, lds_val=lds_val)
     s.add_cnf(cnf.lits, cnf.offsets)
     assert s.solve(a) == SolverResult.Unsat
+    assert_ran_the_build_asked_for(s, one_per_simd, lds_val)
     core = s.core()
     assert_core(core, a, cnf, cnf.n_vars)
     assert 0 < len(core) < len(a)

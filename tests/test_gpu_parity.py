@@ -106,8 +106,7 @@ def test_solver_loop_reaches_the_known_optimum(terrain, pset, k0, kstar):
 def test_rect32_full_cdcl_harder_rungs():
     """configs[2] rungs that finish within seconds: rect 32x32 default at k = 120, 24 and 17 (SAT), and the
     refutations of k = 10 and k = 12 (optimum is 15 per SURVEY §6; PicoSAT needed 24.6 s for k = 12), cross-checked
-    with the oracle.  The whole ladder to the proven optimum takes the GPU ten minutes (profiles/r02_b_ladder32.log)
-    and is not part of the suite."""
+    with the oracle.  The optimum rungs k = 14 (UNSAT) and k = 15 (SAT) are in tests/test_zz_hard_rungs.py."""
     grid = make_grid("rect32x32")
     enc = Encoding.encode(platform_defs("default"), grid)
     for k, want in [(120, SolverResult.Sat), (24, SolverResult.Sat), (17, SolverResult.Sat), (10, SolverResult.Unsat), (12, SolverResult.Unsat)]:

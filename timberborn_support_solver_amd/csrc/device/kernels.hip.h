@@ -9,8 +9,9 @@
 // search over its private slab (layout.h).  A workgroup is a single wave, so
 // there are no workgroup barriers; lanes cooperate through ballots, lane
 // shuffles and LDS:
-//   * BCP propagates up to 8 queue literals per step: the wave splits into G lane
-//     groups (G = 1/2/4/8 by queue length), one dequeued literal per group.  Each
+//   * BCP propagates up to 32 queue literals per step: the wave splits into G lane
+//     groups (G a power of two up to MS_MAX_GROUPS = 32, by queue length and
+//     opts.max_groups), one dequeued literal per group.  Each
 //     group streams that literal's three lists with coalesced reads: binary
 //     implications and ternary literal pairs from the SHARED read-only CSRs
 //     (no watches, no writes), and the private two-watched-literal list of the

@@ -346,6 +346,7 @@ struct mi355sat {
     DevBuf<ms_int2> d_tern_pairs;
     bool lds_val = false;                      // assignment staged in LDS (2 bits/var)
     uint32_t lds_val_bytes = 0;
+    mi355sat_search_build last_build{};        // build of the last search launch (mi355sat_debug_last_search_build)
     DevBuf<char> d_template;
     SlabBuf d_slabs;
     DevBuf<MsState> d_states;
@@ -386,6 +387,13 @@ struct mi355sat {
 };
 
 namespace {
+
+// What the kernels other than the search kernel (BCP, probing) do with the assignment, and the search kernel when
+// opts.lds_val is not on auto: staged in LDS if forced, or on auto when it fits the round-1 budget of 16 workers per CU.
+inline bool staged_in_lds(int opt_lds_val, uint32_t lds_val_bytes) {
+    if (lds_val_bytes > 150 * 1024) return false;
+    return opt_lds_val == 1 || (opt_lds_val == 0 && lds_val_bytes <= 10 * 1024);
+}
 
 // ---- formula preparation ---------------------------------------------------------
 struct Prepared {
@@ -785,8 +793,7 @@ void upload_formula(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_
     // assignment in LDS (2 bits per variable) when it still leaves room for 12 waves per CU
     // (measured on rect 64x64: 12 waves/CU with the assignment in HBM beat 6 waves/CU with it in LDS)
     s.lds_val_bytes = ((P.n_vars + 15) / 16) * 4 + 5 * ((P.n_vars + 31) / 32) * 4;   // 2-bit assignment + five 1-bit maps (marks, current level, level 0, minimisation: failed, queued)
-    s.lds_val = s.opts.lds_val == 1 || (s.opts.lds_val == 0 && s.lds_val_bytes <= 10 * 1024);
-    if (s.lds_val_bytes > 150 * 1024) s.lds_val = false;
+    s.lds_val = staged_in_lds(s.opts.lds_val, s.lds_val_bytes);
     // worker count limited by free HBM
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -1392,6 +1399,36 @@ void fetch_model(mi355sat& s, uint32_t worker, std::vector<int8_t>& out, uint64_
 
 struct SliceResult { float ms; };
 
+// Which build a launch of `active` workers runs, and with how much dynamic LDS: the one place that decides it (launch_slice
+// follows it; mi355sat_debug_search_build_rule evaluates it without a launch).  mode 0 = search, else BCP / probing
+// (wps 0: those kernels have one build per LDS variant).
+//   lds: assignment (2 bits / variable) and analysis marks (1 bit) in LDS when this launch's workers per CU leave room
+//        (160 KB per CU, 150 KB of it budgeted; a workgroup's static LDS aside: 5.2 KB, 13.2 KB in the builds with the sort
+//        buffer): 16 workers per CU -> 3.4 KB each, one per CU -> up to 64 KB, which covers rect 64x64.  State is written
+//        back to HBM at every slice end, so consecutive launches may differ.  The budget is SIGNED: above 25 workers per CU
+//        the reserve exceeds the share and nothing is staged.
+//   wps: the build compiled for the launch's waves per SIMD: 1 (<= 1024 workers: the SIMD's whole register file, everything
+//        inlined), 2 (<= 2048: no spills either), else the full fleet's.
+inline mi355sat_search_build choose_build(uint32_t active, uint32_t lds_val_bytes, bool staged, int opt_lds_val, int opt_one_per_simd, int mode) {
+    mi355sat_search_build b{};
+    b.active = active;
+    b.lds_val_bytes = lds_val_bytes;
+    bool lds = staged;
+    if (mode == 0 && opt_lds_val == 0) {
+        const int64_t per_cu = ((int64_t)active + 255) / 256;
+        const int64_t budget = std::max<int64_t>(0, std::min<int64_t>(64 * 1024, 150 * 1024 / per_cu - (per_cu <= 8 ? 14 : 6) * 1024));
+        lds = (int64_t)lds_val_bytes <= budget;
+    }
+    b.lds = lds ? 1 : 0;
+    b.dyn_lds_bytes = lds ? lds_val_bytes : 0;
+    if (mode == 0) {
+        int wps = opt_one_per_simd < 0 ? MS_SEARCH_WAVES_PER_SIMD : (active <= 1024 ? 1 : (active <= 2048 ? 2 : MS_SEARCH_WAVES_PER_SIMD));
+        if (opt_one_per_simd == 2 || opt_one_per_simd == 4) wps = std::max(wps, opt_one_per_simd == 2 ? 2 : MS_SEARCH_WAVES_PER_SIMD);   // (A/B: a build for more waves)
+        b.wps = wps;
+    }
+    return b;
+}
+
 SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_refuted = true, uint32_t active = 0, int auto_slice_ms = 20) {
     if (active == 0 || active > s.n_alloc) active = s.n_alloc;   // workers [0, active) run this slice
     MsParams prm{};
@@ -1427,22 +1464,17 @@ SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_r
         prm.share_max_len = s.opts.share_len > 0 ? (uint32_t)s.opts.share_len : (uint32_t)MS_SHARE_MAXLEN;
         prm.share_interval = s.opts.share_interval > 0 ? (uint32_t)s.opts.share_interval : 0xffffffffu;
     }
-    // Assignment (2 bits / variable) and analysis marks (1 bit) in LDS when this launch's workers per CU leave room
-    // (160 KB per CU; a workgroup's static 3 KB aside): 16 workers per CU -> 9 KB each (the round-1 rule), one per CU
-    // -> up to 64 KB, which covers rect 64x64.  State is written back to HBM at every slice end, so consecutive
-    // launches may differ.
-    bool lds = s.lds_val;
-    if (mode == 0 && s.opts.lds_val == 0) {
-        const uint32_t per_cu = (active + 255) / 256;
-        lds = s.lds_val_bytes <= std::min<uint32_t>(64 * 1024, 150 * 1024 / per_cu - (per_cu <= 8 ? 14 : 6) * 1024);   // (a workgroup's static LDS aside: 5.2 KB, 13.2 KB in the builds with the sort buffer)
-    }
-    const uint32_t dyn = lds ? s.lds_val_bytes : 0;
+    const mi355sat_search_build build = choose_build(active, s.lds_val_bytes, s.lds_val, s.opts.lds_val, s.opts.one_per_simd, mode);
+    const bool lds = build.lds != 0;
+    const uint32_t dyn = build.dyn_lds_bytes;
     HIPCHK(hipEventRecord(s.ev0, s.stream));
     if (mode == 0) {
-        // the build compiled for the launch's waves per SIMD: 1 (<= 1024 workers: the SIMD's whole register file, everything
-        // inlined), 2 (<= 2048: no spills either), else the full fleet's
-        int wps = s.opts.one_per_simd < 0 ? MS_SEARCH_WAVES_PER_SIMD : (active <= 1024 ? 1 : (active <= 2048 ? 2 : MS_SEARCH_WAVES_PER_SIMD));
-        if (s.opts.one_per_simd == 2 || s.opts.one_per_simd == 4) wps = std::max(wps, s.opts.one_per_simd == 2 ? 2 : MS_SEARCH_WAVES_PER_SIMD);   // (A/B: a build for more waves)
+        const int wps = build.wps;
+        const uint64_t n_launches = s.last_build.launches;
+        const uint32_t seen = s.last_build.builds_seen;
+        s.last_build = build;
+        s.last_build.launches = n_launches + 1;
+        s.last_build.builds_seen = seen | (1u << ((lds ? 3 : 0) + (wps == 1 ? 0 : (wps == 2 ? 1 : 2))));
 #define MS_LAUNCH_SEARCH(LVV, W) hipLaunchKernelGGL((ms_search_kernel<LVV, W>), dim3(active), dim3(MS_WAVE), (LVV) ? dyn : 0, s.stream, s.sh, s.L, s.d_slabs.p, prm)
         if (lds) {
             if (wps == 1) MS_LAUNCH_SEARCH(true, 1);
@@ -2525,6 +2557,20 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
         return w <= cap_words || !out ? 0 : MI355SAT_ERR_ARG;
     } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
     catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+}
+
+int mi355sat_debug_last_search_build(const mi355sat* s, mi355sat_search_build* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    if (s->last_build.launches == 0) return MI355SAT_ERR_STATE;
+    *out = s->last_build;
+    return 0;
+}
+
+int mi355sat_debug_search_build_rule(uint32_t active, uint32_t lds_val_bytes, int32_t staged, int32_t lds_val, int32_t one_per_simd,
+                                     int32_t mode, mi355sat_search_build* out) {
+    if (!out || active == 0) return MI355SAT_ERR_ARG;
+    *out = choose_build(active, lds_val_bytes, staged < 0 ? staged_in_lds(lds_val, lds_val_bytes) : staged != 0, lds_val, one_per_simd, mode);
+    return 0;
 }
 
 // ---- clause exchange between handles (GPUs) working on the SAME formula ------------------------------------------------

@@ -59,6 +59,17 @@ class Mi355SatStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatSearchBuild(ctypes.Structure):   # mi355sat_search_build (test hook)
+    _fields_ = [("lds", ctypes.c_int32), ("wps", ctypes.c_int32), ("dyn_lds_bytes", ctypes.c_uint32), ("active", ctypes.c_uint32),
+                ("lds_val_bytes", ctypes.c_uint32), ("builds_seen", ctypes.c_uint32), ("launches", ctypes.c_uint64)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        # every (lds, wps) the handle has launched so far
+        d["builds"] = {(l, w) for l in (0, 1) for i, w in enumerate((1, 2, 4)) if d["builds_seen"] >> (3 * l + i) & 1}
+        return d
+
+
 def algorithmic_bytes(stats):
     """12*n_deq + 9*n_watch + 5*n_cl_lit + 8*n_move + 13*n_enq."""
     return (12 * stats["n_deq"] + 9 * stats["n_watch"] + 5 * stats["n_cl_lit"] + 8 * stats["n_move"]
@@ -103,6 +114,9 @@ def _bind(L):
     L.mi355sat_stats.argtypes = [vp, ctypes.POINTER(Mi355SatStats)]
     L.mi355sat_set_proof_path.argtypes = [vp, ctypes.c_char_p]
     L.mi355sat_debug_share_ring.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_debug_last_search_build.argtypes = [vp, ctypes.POINTER(Mi355SatSearchBuild)]
+    L.mi355sat_debug_search_build_rule.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_share_export.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_share_import.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     return L
@@ -308,6 +322,25 @@ class Mi355Sat:
             else:
                 cur.append(l)
         return out
+
+    def debug_last_search_build(self):
+        """Test hook: the build of the search kernel this handle's last search launch ran, as a dict (lds 0/1, wps 1/2/4,
+        dyn_lds_bytes, active, lds_val_bytes, launches, builds = every (lds, wps) launched so far)."""
+        b = Mi355SatSearchBuild()
+        self._check(self._L.mi355sat_debug_last_search_build(self._h, ctypes.byref(b)), "debug_last_search_build")
+        return b.as_dict()
+
+    @staticmethod
+    def debug_search_build_rule(active, lds_val_bytes, lds_val=0, one_per_simd=0, mode=0, staged=-1, _lib_override=None):
+        """Test hook: the selection rule alone (nothing is launched): the build a launch of `active` workers would run."""
+        raw = _lib_override if _lib_override is not None else _lib.solver_lib()
+        if id(raw) not in _bound:
+            _bound[id(raw)] = _bind(raw)
+        b = Mi355SatSearchBuild()
+        rc = _bound[id(raw)].mi355sat_debug_search_build_rule(active, lds_val_bytes, staged, lds_val, one_per_simd, mode, ctypes.byref(b))
+        if rc < 0:
+            raise SolverError(f"debug_search_build_rule failed ({rc})")
+        return b.as_dict()
 
     def share_export(self, max_words=1 << 20):
         """The clauses this handle's workers passed on since the last call, for handles on OTHER GPUs that search the same
