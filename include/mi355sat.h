@@ -302,6 +302,52 @@ int mi355sat_debug_last_search_build(const mi355sat* s, mi355sat_search_build* o
 int mi355sat_debug_search_build_rule(uint32_t active, uint32_t lds_val_bytes, int32_t staged, int32_t lds_val,
                                      int32_t one_per_simd, int32_t mode, mi355sat_search_build* out);
 
+/* --- warm incremental solve ------------------------------------------------ */
+/* on != 0: mi355sat_solve() keeps what the solve before it built and learnt.  Default off: every solve prepares the
+ * formula from scratch, as documented above.  With it on, a solve starts WARM when the workers of the handle's previous
+ * mi355sat_solve() are still on the device and only clauses and / or assumptions were added since: no simplification,
+ * no upload, no reset - the new clauses are mapped to device literals and attached to every resident worker
+ * (ms_attach_kernel), the assumptions are rewritten, and the search goes on with every worker's learnt clauses, saved
+ * phases, decision order, restart averages and the exchange ring.  Otherwise it starts COLD (the path above, unchanged);
+ * the fallback is silent and counted (mi355sat_debug_incremental).  A solve starts cold when
+ *   - it is the handle's first, or the one before it failed;
+ *   - a new clause or assumption names a variable above the highest one of the last cold start (mi355sat_reserve()
+ *     the variables you are going to need BEFORE the first solve to avoid this);
+ *   - a new clause or assumption names a variable that opts.simp = 2 eliminated;
+ *   - there are more assumptions than the slabs have room for (the count at the last cold start + 256);
+ *   - a proof path is set, or opts.cube_split is on;
+ *   - the clauses attached warm since the last cold start would take more than a quarter of a worker's learnt-clause
+ *     slots or literal store (they are kept there for ever), or a worker's store or watch pool ran full attaching them;
+ *   - mi355sat_solve_batch(), mi355sat_sweep_begin() or mi355sat_propagate_batch() ran on the handle in between (they
+ *     stay cold and take the device state over).
+ * A handle whose formula was refuted without assumptions answers every later solve UNSAT with the empty core at once.
+ * The IPASIR state rules do not change: assumptions are consumed, failed / core are valid straight after UNSAT only,
+ * an interrupt is not lost; an interrupted or budget-exhausted solve leaves the handle warm.  Returns 0. */
+int mi355sat_set_incremental(mi355sat* s, int on);
+
+#define MI355SAT_COLD_NONE 0            /* no cold start yet */
+#define MI355SAT_COLD_FIRST 1           /* nothing resident: first solve, or the solve before failed */
+#define MI355SAT_COLD_NEW_VAR 2
+#define MI355SAT_COLD_ELIMINATED 3
+#define MI355SAT_COLD_PROOF 4
+#define MI355SAT_COLD_CUBE_SPLIT 5
+#define MI355SAT_COLD_PINNED_SHARE 6
+#define MI355SAT_COLD_OTHER_SEARCH 7    /* solve_batch / sweep_* / propagate_batch in between */
+#define MI355SAT_COLD_ASSUMP_CAP 8
+#define MI355SAT_COLD_DEVICE_FULL 9     /* a worker's learnt store or watch pool ran full during the attach */
+/* Test hook: what the incremental mode did on this handle so far. */
+typedef struct mi355sat_incremental_info {
+    int32_t  enabled;
+    int32_t  last_cold_reason;     /* MI355SAT_COLD_* of the last solve() that started cold with the mode on */
+    uint64_t warm_solves;          /* solve() calls that started warm (or were answered from a refuted formula) */
+    uint64_t cold_solves;          /* solve() calls that started cold with the mode on */
+    uint64_t attached_clauses;     /* clauses of two and more literals handed to the resident workers so far */
+    uint64_t attached_units;       /* one-literal clauses handed to them so far */
+    uint64_t resident_learnts;     /* learnt clauses in the workers' stores when the last warm solve began, summed */
+    uint64_t attach_launches;      /* ms_attach_kernel launches so far */
+} mi355sat_incremental_info;
+int mi355sat_debug_incremental(const mi355sat* s, mi355sat_incremental_info* out);
+
 /* Clause exchange BETWEEN handles that search the SAME formula - the replicas of the sharded loop's last bounds, one
  * handle per GPU (every rank poses the reference's next bound, crates/repl/src/main.rs:292-295, with its own
  * seed).  Inside one handle the workers pass their short / low-LBD learnt clauses on through a ring on the device;

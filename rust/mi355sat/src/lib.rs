@@ -51,6 +51,7 @@ extern "C" {
     fn mi355sat_core(s: *mut c_void, out: *mut i32, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
+    fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
 }
 
 pub struct Mi355Sat { h: *mut c_void }
@@ -70,6 +71,15 @@ impl Mi355Sat {
             anyhow::bail!("mi355sat_new failed: {}", m.to_string_lossy());
         }
         Ok(Self { h })
+    }
+    /// Warm incremental solve (`mi355sat_set_incremental`): with it on, a `solve` / `solve_assumps` after clauses or
+    /// assumptions were added goes on with the workers of the solve before - learnt clauses, phases, decision order -
+    /// instead of preparing the formula from scratch (silently cold where that is not possible: include/mi355sat.h).
+    /// Users of `SolveIncremental` want it on; `reserve` the variables of later clauses before the first solve.
+    /// Replayed in C by tests/abi_incremental.c.
+    pub fn set_incremental(&mut self, on: bool) -> anyhow::Result<()> {
+        if unsafe { mi355sat_set_incremental(self.h, on as c_int) } < 0 { return Err(self.err()); }
+        Ok(())
     }
     fn err(&self) -> anyhow::Error {
         let m = unsafe { std::ffi::CStr::from_ptr(mi355sat_last_error(self.h)) };

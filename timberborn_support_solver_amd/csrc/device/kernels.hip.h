@@ -1888,6 +1888,9 @@ template <bool LV>
 DEV void wk_store(Wk& w, const MsShared& sh, const MsLayout& L, u64 cycles) {
     u64 cl = wave_sum_u32(w.c_cl_lit);
     lds_fence();
+    // (LV) The staged assignment goes back to the slab's bytes; the level bitmaps are derived data (rebuilt from the trail
+    // when a slice begins) and the variable records were written in the slab all along.  So BETWEEN slices the slab's
+    // `val` and `vrec` are authoritative in every build - what ms_attach_kernel and ms_final_kernel rely on.
     if (LV) {
         Gp<uint4> gv = (Gp<uint4>)WKA(uint8_t, val);
         const uint32_t words = (sh.n_vars + 15) >> 4;
@@ -2728,4 +2731,67 @@ __global__ __launch_bounds__(MS_WAVE) void ms_final_kernel(MsShared sh, MsLayout
     }
     sync();
     if (lane == 0) ok[b] = bad ? 0 : 1;
+}
+
+// ---- warm attach (incremental solve) ---------------------------------------------------
+// Clauses the caller added between two solves of one handle go to the workers that are still resident from the solve
+// before (mi355sat_set_incremental): one workgroup (one wave) per worker, between two slices.  Clause c is
+// lits[offs[c] .. offs[c + 1]), device literals, each variable at most once per clause (the host sorts and dedupes).
+// The worker goes to decision level 0 first - whatever its last slice left: a model, a refuted cube, a search path.
+// Between slices the slab is the whole truth also for the LDS builds (wk_store writes the staged assignment back and
+// the level bitmaps are rebuilt from the trail when a slice begins), so this kernel has one build and touches the
+// assignment bytes and the variable records only.  Then one clause per step, one literal per lane, 64 literals per
+// round, under the level-0 assignment as import_shared does it: satisfied -> nothing to do; no free literal -> the
+// formula is refuted (MS_ST_UNSAT); one -> a level-0 fact, left in the queue for the next slice's BCP; otherwise the free
+// literals become a learnt clause of LBD 1, which reduce_db keeps for ever (lbd <= 2), marked MS_LBD_NOLOG (a "learnt"
+// clause no proof line stands for).  A full store or watch pool ends in MS_ST_ERR_*: the host starts that solve cold.
+// Only workers that are MS_ST_RUNNING are touched: the host sets that (ms_assign_kernel) before a warm solve, and a
+// worker fresh from the template is.
+__global__ __launch_bounds__(MS_WAVE) void ms_attach_kernel(MsShared sh, MsLayout L, char* slabs, uint32_t wid0, uint32_t n_workers,
+                                                           const int32_t* lits, const uint32_t* offs, uint32_t c0, uint32_t c1) {
+    __shared__ int32_t s_ring[MS_LDS_RING];
+    __shared__ uint32_t s_hist[64];
+    __shared__ uint32_t s_ov;
+    const uint32_t wid = blockIdx.x + wid0;   // workers [wid0, n_workers)
+    if (wid >= n_workers) return;
+    Wk w;
+    w.lane = (int)threadIdx.x;
+    w.ring = (LdsI32)s_ring; w.hist = (LdsU32)s_hist; w.ov_cnt = (LdsU32)&s_ov;   // (what enqueue_uniform and reduce_db use)
+    w.claim = nullptr; w.lval = nullptr; w.lseen = nullptr; w.lcur = nullptr; w.lzero = nullptr; w.lfail = nullptr; w.lq = nullptr;
+    w.mcnt = nullptr; w.bfl = nullptr; w.tl = nullptr; w.jd = nullptr;
+    if (w.lane == 0) s_ov = 0;
+    MsParams prm{};
+    prm.max_groups = 1;
+    wk_bind<false>(w, sh, L, slabs + (size_t)wid * L.slab_bytes, prm);
+    wk_uniformize(w);
+    lds_fence();
+    if (w.status != MS_ST_RUNNING) return;
+    cancel_until<false>(w, sh, L, 0);
+    Gp<const int32_t> cl = (Gp<const int32_t>)lits;
+    Gp<const uint32_t> co = (Gp<const uint32_t>)offs;
+    Gp<int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
+    for (uint32_t c = c0; c < c1 && w.status == MS_ST_RUNNING; c++) {
+        const uint32_t b = (uint32_t)uni((int)co[c]), e = (uint32_t)uni((int)co[c + 1]);
+        bool sat = false, bad = false;
+        int cnt = 0;
+        for (uint32_t k0 = b; k0 < e && !sat && !bad; k0 += MS_WAVE) {
+            const uint32_t k = k0 + (uint32_t)w.lane;
+            const bool in = k < e;
+            const int lit = in ? cl[k] : 0;
+            const bool ok = (uint32_t)lit < 2u * sh.n_vars;
+            const int v = in && ok ? lit_value<false>(w, sh, L, lit) : MS_VAL_FALSE;   // units attached before are visible
+            bad = ballot(in && !ok) != 0;
+            sat = ballot(in && v == MS_VAL_TRUE) != 0;
+            const u64 free_m = ballot(in && v == MS_VAL_UNDEF);
+            if ((free_m >> w.lane) & 1) learnt_buf[cnt + popc64(free_m & lanemask_lt(w.lane))] = lit;
+            cnt += popc64(free_m);
+        }
+        wave_fence();
+        if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
+        if (sat) continue;
+        if (cnt == 0) { w.status = MS_ST_UNSAT; break; }           // falsified at level 0
+        if (cnt == 1) enqueue_uniform<false>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE);
+        else if (add_learnt<false>(w, sh, L, cnt, 1u | MS_LBD_NOLOG) < 0) break;
+    }
+    wk_store<false>(w, sh, L, 0);
 }

@@ -191,4 +191,78 @@ std::vector<LoopIteration> solver_loop_sweep(const WorldGrid& world, const Encod
     return hist;
 }
 
+std::vector<LoopIteration> solver_loop_incremental(const WorldGrid& world, const Encoding& encoding, const PlatformLimits& limits,
+                                                   const mi355sat_opts* opts,
+                                                   const std::function<void(const std::string&)>& out,
+                                                   const std::function<void(mi355sat*)>& on_interrupter) {
+    const Dims one{1, 1};
+    if (limits.card_limits.size() != 1 || !limits.card_limits.count(one) || !limits.weights.empty() || limits.has_weight_limit)
+        throw std::runtime_error("solver_loop_incremental handles a single 1x1 cardinality limit; use solver_loop");
+    std::vector<LoopIteration> hist;
+    size_t k = limits.card_limits.at(one);
+    mi355sat* s = nullptr;
+    Cnf cnf;
+    std::vector<int32_t> card;
+    auto release = [&]() {
+        if (s && on_interrupter) on_interrupter(nullptr);   // the handle is about to die
+        if (s) mi355sat_free(s);
+        s = nullptr;
+    };
+    auto fail = [&](const char* ctx) {
+        std::string m = std::string(ctx) + ": " + mi355sat_last_error(s);
+        release();
+        throw std::runtime_error(m);
+    };
+    for (;;) {
+        if (s && k < card.size()) {
+            const int32_t unit[2] = {-card[k], 0};              // at most k  <=>  not (at least k+1)
+            for (int32_t l : unit) if (mi355sat_add(s, l) < 0) fail("Failed to add the bound");
+        } else {
+            release();
+            PlatformLimits lim;
+            lim.card_limits[one] = k;
+            std::vector<std::vector<int32_t>> outs;
+            cnf = encoding.with_limits(lim).into_cnf(&outs);
+            card = outs.empty() ? std::vector<int32_t>{} : outs[0];
+            s = mi355sat_new(opts);
+            if (!s) throw std::runtime_error(std::string("Failed to create solver: ") + mi355sat_last_error(nullptr));
+            mi355sat_set_incremental(s, 1);
+            if (mi355sat_add_cnf(s, cnf.lits.data(), cnf.offsets.data(), cnf.n_clauses()) < 0) fail("Failed to add CNF");
+            mi355sat_reserve(s, cnf.n_vars);
+        }
+        if (on_interrupter) on_interrupter(s);
+        LoopIteration it;
+        it.k = k;
+        auto t0 = std::chrono::steady_clock::now();
+        const int rc = mi355sat_solve(s);
+        if (rc < 0) fail("solve");
+        it.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        it.result = (SolverResult)rc;
+        mi355sat_stats(s, &it.stats);
+        if (it.result != SolverResult::Sat) {
+            out(it.result == SolverResult::Unsat ? "No solution found for the current constraints" : "Solver interrupted");
+            hist.push_back(std::move(it));
+            break;
+        }
+        std::vector<int8_t> model(cnf.n_vars, 0);
+        if (mi355sat_model(s, model.data(), cnf.n_vars) < 0) fail("full_solution");
+        it.layout = PlatformLayout::from_assignment(model.data(), encoding.instance().n_vars, encoding);
+        it.count = it.layout.platform_count();
+        if (it.count == 0) {
+            out("Found a solution with no platforms - aborting");
+            hist.push_back(std::move(it));
+            break;
+        }
+        k = it.count - 1;
+        out("Solution found (" + std::to_string(it.count) + " platforms total)");
+        for (auto& kv : it.layout.platform_stats())
+            out(std::to_string(kv.first.w) + "x" + std::to_string(kv.first.h) + ": " + std::to_string(kv.second));
+        it.valid = it.layout.validate(world).is_valid();
+        out(it.valid ? "Solution validation OK" : "Solution validation FAILED");
+        hist.push_back(std::move(it));
+    }
+    release();
+    return hist;
+}
+
 }  // namespace tbs

@@ -49,4 +49,14 @@ std::vector<LoopIteration> solver_loop_sweep(const WorldGrid& world, const Encod
                                              const std::function<void(mi355sat*)>& on_interrupter = {},
                                              const std::atomic<int>* interrupted = nullptr);
 
+// The reference's loop over ONE solver handle in its warm incremental mode (mi355sat_set_incremental): one CNF with the
+// totalizer built for the first bound, every tighter bound a UNIT on that totalizer's output (the literal the batch above
+// assumes, added for good), then mi355sat_solve() again on the workers of the solve before.  Same messages, same order,
+// same on_interrupter contract as solver_loop.  A first bound that needs no totalizer leaves nothing to tighten: the next
+// bound then gets a handle and a CNF of its own.  Only the `-l1:K` form.  Opt-in (tbs_cli --incremental).
+std::vector<LoopIteration> solver_loop_incremental(const WorldGrid& world, const Encoding& encoding, const PlatformLimits& limits,
+                                                   const mi355sat_opts* opts,
+                                                   const std::function<void(const std::string&)>& out,
+                                                   const std::function<void(mi355sat*)>& on_interrupter = {});
+
 }  // namespace tbs

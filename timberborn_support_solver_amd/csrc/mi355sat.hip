@@ -384,6 +384,23 @@ struct mi355sat {
     bool core_valid = false;
     std::vector<std::vector<int32_t>> batch_cores;   // of the last solve_batch(), per instance
     std::vector<uint8_t> batch_core_valid;
+    // warm incremental solve (mi355sat_set_incremental): what the last mi355sat_solve() left on the device, and what was
+    // attached to it since
+    struct Incremental {
+        bool on = false;
+        bool resident = false;                 // the slabs hold the workers of the last solve(); they know clauses [0, n_clauses)
+        bool refuted = false;                  // the formula is UNSAT whatever the assumptions (it only grows)
+        int why_not = MI355SAT_COLD_FIRST;     // why nothing is resident
+        size_t n_clauses = 0;                  // clauses of lits / offs above that the resident workers hold: uploaded or attached
+        std::vector<uint8_t> eliminated;       // per caller variable: resolved away before the upload (opts.simp = 2)
+        std::vector<int32_t> lits;             // every clause attached since the upload, device literals: workers created
+        std::vector<uint32_t> offs{0};         // later (ramp-up, grow_workers) start from the template and get all of them
+        uint64_t pinned = 0, pinned_lits = 0;  // those of two and more literals, and the room they take in a worker's lc_lits
+        std::vector<MsState> base;             // the workers' counters when the last solve ended (they run on)
+        mi355sat_incremental_info info{};
+    } inc;
+    DevBuf<int32_t> d_inc_lits;
+    DevBuf<uint32_t> d_inc_offs;
 };
 
 namespace {
@@ -1606,7 +1623,38 @@ struct Sweep {
     std::vector<std::vector<uint8_t>> core_flag;
     DevBuf<int32_t> d_fw, d_fok;
     DevBuf<uint32_t> d_fout, d_fscratch;
+    // warm incremental solve: a plain solve() that may leave its workers to the next one (a cold start) or took them over
+    // from the one before (a warm start: their counters run on from counters0, conflicts0 = those conflicts summed)
+    bool keep_warm = false;
+    std::vector<MsState> counters0;
+    uint64_t conflicts0 = 0;
 };
+
+// Caller's assumption lists -> device literals: equivalent-literal substitution, then the device's variable order (perm);
+// each literal at most once per instance (a repeated assumption would open a level of its own: a list longer than n_vars
+// would overrun trail_lim).  base_src keeps where each one came from in the caller's list of its instance.
+void map_assumptions(const mi355sat& s, const std::vector<uint32_t>& perm, uint32_t n_vars, const std::vector<int32_t>& assump,
+                     const std::vector<uint64_t>& assump_off, uint32_t n_instances, std::vector<int32_t>& a_int,
+                     std::vector<uint64_t>& a_off, std::vector<uint32_t>& base_src) {
+    a_int.clear();
+    a_off.assign(1, 0);
+    base_src.clear();
+    std::vector<uint32_t> stamp(2 * (size_t)n_vars, 0);
+    for (uint32_t i = 0; i < n_instances; i++) {
+        for (uint64_t k = assump_off[i]; k < assump_off[i + 1]; k++) {
+            int32_t d = assump[k];
+            if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > n_vars) throw HipErr{"assumption literal out of range"};
+            int32_t l = to_internal(d);
+            while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);     // a variable replaced by an equivalent literal
+            l = 2 * (int32_t)perm[l >> 1] | (l & 1);
+            if (stamp[l] == i + 1) continue;
+            stamp[l] = i + 1;
+            a_int.push_back(l);
+            base_src.push_back((uint32_t)(k - assump_off[i]));
+        }
+        a_off.push_back(a_int.size());
+    }
+}
 
 int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
                 uint32_t n_instances, bool stop_at_first) {
@@ -1659,32 +1707,14 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     s.d_proof_len.release();
     s.proof_cap = 0;
     sw.split = s.opts.cube_split > 0 && want > n_instances;   // opt-in: see DESIGN.md (measured: not yet a win)
-    // device literals, each at most once per instance (a repeated assumption would open a level of its own: a list longer
-    // than n_vars would overrun trail_lim); base_src keeps where each one came from in the caller's list
     std::vector<int32_t> a_int;
-    std::vector<uint64_t> a_off{0};
-    sw.base_src.clear();
-    {
-        std::vector<uint32_t> stamp(2 * (size_t)P.n_vars, 0);
-        for (uint32_t i = 0; i < n_instances; i++) {
-            for (uint64_t k = assump_off[i]; k < assump_off[i + 1]; k++) {
-                int32_t d = assump[k];
-                if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > P.n_vars) throw HipErr{"assumption literal out of range"};
-                int32_t l = to_internal(d);
-                while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);     // a variable replaced by an equivalent literal
-                l = 2 * (int32_t)P.perm[l >> 1] | (l & 1);
-                if (stamp[l] == i + 1) continue;
-                stamp[l] = i + 1;
-                a_int.push_back(l);
-                sw.base_src.push_back((uint32_t)(k - assump_off[i]));
-            }
-            a_off.push_back(a_int.size());
-        }
-    }
+    std::vector<uint64_t> a_off;
+    map_assumptions(s, P.perm, P.n_vars, assump, assump_off, n_instances, a_int, a_off, sw.base_src);
     uint32_t max_assumps = 0;
     for (uint32_t i = 0; i < n_instances; i++)
         max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)(a_off[i + 1] - a_off[i]));
-    const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps;
+    // (a solve that may be followed by warm ones leaves room for their assumption lists)
+    const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps + (sw.keep_warm ? 256u : 0u);
     const uint32_t initial = (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) ? std::max(256u, n_instances) / n_instances * n_instances : 0;
     upload_formula(s, P, assump_cap, 0, want, initial);
     if (s.n_workers < n_instances) throw HipErr{"not enough device memory for one worker per instance"};
@@ -1904,6 +1934,140 @@ int final_cores(mi355sat& s, Sweep& sw, const std::vector<int32_t>& fw) {
     return 0;
 }
 
+// ---- warm incremental solve ----------------------------------------------------------------------------------------
+// Clauses [c0, c1) of inc.lits / inc.offs (on the device already) to workers [from, to): ms_attach_kernel, on the stream.
+void attach_clauses(mi355sat& s, uint32_t from, uint32_t to, uint32_t c0, uint32_t c1) {
+    if (to <= from) return;
+    hipLaunchKernelGGL(ms_attach_kernel, dim3(to - from), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, from, to,
+                       (const int32_t*)s.d_inc_lits.p, (const uint32_t*)s.d_inc_offs.p, c0, c1);
+    HIPCHK(hipGetLastError());
+    s.inc.info.attach_launches++;
+}
+
+// Start a plain solve() on the workers the one before left on the device: nothing is simplified, built, uploaded or reset.
+// The clauses added since go through the mapping the upload gave the assumptions (s.subst, then s.perm) and are attached
+// to every resident worker; every worker gets the new assumption list and MS_ST_RUNNING (ms_assign_kernel) and keeps its
+// learnt clauses, saved phases, decision order, restart averages and its position in the exchange ring.  Returns
+// MI355SAT_COLD_NONE with sw ready for sweep_step() (or decided already), or the reason why this solve has to start cold
+// (nothing on the device has changed then, except after MI355SAT_COLD_DEVICE_FULL).
+int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off) {
+    mi355sat::Incremental& I = s.inc;
+    if (!s.proof_path.empty()) return MI355SAT_COLD_PROOF;
+    if (s.opts.cube_split > 0) return MI355SAT_COLD_CUBE_SPLIT;
+    if (!I.resident) return I.why_not;
+    // the caller's literal on the device, or the reason why it has none
+    auto map_lit = [&](int32_t d, int32_t& out) -> int {
+        const uint64_t v = (uint64_t)(d < 0 ? -(int64_t)d : d);
+        if (v > s.n_vars) return MI355SAT_COLD_NEW_VAR;
+        int32_t l = to_internal(d);
+        while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
+        if (I.eliminated[l >> 1]) return MI355SAT_COLD_ELIMINATED;
+        out = 2 * (int32_t)s.perm[l >> 1] | (l & 1);
+        return 0;
+    };
+    int32_t l = 0;
+    for (int32_t d : assump) if (int why = map_lit(d, l)) return why;
+    std::vector<int32_t> a_int;
+    std::vector<uint64_t> a_off;
+    std::vector<uint32_t> base_src;
+    map_assumptions(s, s.perm, s.n_vars, assump, assump_off, 1, a_int, a_off, base_src);
+    if (a_int.size() > s.L.assump_cap) return MI355SAT_COLD_ASSUMP_CAP;
+    // the clauses added since the workers last heard of any: sorted, without repeated literals and tautologies
+    const size_t nc = s.offs.size() - 1;
+    std::vector<int32_t> nl, tmp;
+    std::vector<uint32_t> no;
+    uint64_t units = 0, pinned = 0, pinned_lits = 0;
+    bool empty_clause = false;
+    for (size_t c = I.n_clauses; c < nc; c++) {
+        tmp.clear();
+        for (uint64_t k = s.offs[c]; k < s.offs[c + 1]; k++) {
+            if (int why = map_lit(s.lits[k], l)) return why;
+            tmp.push_back(l);
+        }
+        std::sort(tmp.begin(), tmp.end());
+        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+        bool taut = false;
+        for (size_t i = 0; i + 1 < tmp.size(); i++) if ((tmp[i] ^ 1) == tmp[i + 1]) taut = true;
+        if (taut) continue;
+        if (tmp.empty()) { empty_clause = true; continue; }
+        if (tmp.size() == 1) units++;
+        else { pinned++; pinned_lits += (tmp.size() + 3) & ~(size_t)3; }
+        nl.insert(nl.end(), tmp.begin(), tmp.end());
+        no.push_back((uint32_t)nl.size());
+    }
+    // attached clauses are never dropped (reduce_db keeps LBD <= 2): they may take a quarter of a worker's learnt store
+    if (I.pinned + pinned > s.L.learnt_cap / 4 || I.pinned_lits + pinned_lits > s.L.learnt_lit_cap / 4) return MI355SAT_COLD_PINNED_SHARE;
+
+    // from here on the solve is warm
+    const uint32_t c0 = (uint32_t)(I.offs.size() - 1);
+    for (uint32_t o : no) I.offs.push_back((uint32_t)I.lits.size() + o);
+    I.lits.insert(I.lits.end(), nl.begin(), nl.end());
+    const uint32_t c1 = (uint32_t)(I.offs.size() - 1);
+    I.pinned += pinned;
+    I.pinned_lits += pinned_lits;
+    I.n_clauses = nc;
+    sw.n_instances = 1;
+    sw.stop_at_first = true;
+    sw.decided = 0;
+    sw.active = false;
+    sw.results.assign(1, MI355SAT_INTERRUPTED);
+    sw.winner.assign(1, -1);
+    sw.dropped.assign(1, 0);
+    sw.n_moved = 0;
+    sw.ramp_ms = 0;
+    sw.split = false;
+    sw.core_flag.assign(sw.cores ? 1 : 0, std::vector<uint8_t>(assump.size(), 0));
+    sw.base_src = base_src;
+    sw.base_assump = a_int;
+    sw.base_off = a_off;
+    const uint32_t W = s.n_workers;
+    sw.w_inst.assign(W, 0);
+    sw.w_cube.assign(W, a_int);
+    sw.w_busy.assign(W, 1);
+    sw.w_conf0.assign(W, 0);
+    sw.open.assign(1, W);
+    sw.counters0 = I.base;
+    sw.counters0.resize(W, MsState{});
+    sw.conflicts0 = 0;
+    I.info.resident_learnts = 0;
+    for (const MsState& st : sw.counters0) { sw.conflicts0 += st.conflicts; I.info.resident_learnts += st.n_learnts; }
+    I.info.attached_clauses += pinned;
+    I.info.attached_units += units;
+    if (empty_clause) {
+        I.refuted = true;
+        sw.results[0] = MI355SAT_UNSAT;
+        sw.decided = 1;
+        return MI355SAT_COLD_NONE;
+    }
+    // the assumption list: to every resident worker now, and where grow_workers takes it from for the workers it creates
+    s.d_assump.upload(a_int.empty() ? std::vector<int32_t>{0} : a_int, s.stream);
+    s.d_assump_off.upload(a_off, s.stream);
+    std::vector<int32_t> upd;
+    for (uint32_t w = 0; w < s.n_alloc; w++) upd.insert(upd.end(), {(int32_t)w, MS_ST_RUNNING, 1, (int32_t)a_int.size(), 0});
+    sw.d_upd.upload(upd, s.stream);
+    hipLaunchKernelGGL(ms_assign_kernel, dim3(s.n_alloc), dim3(64), 0, s.stream, s.L, s.d_slabs.p, s.n_alloc, sw.d_upd.p, s.d_assump.p);
+    HIPCHK(hipGetLastError());
+    s.d_inc_lits.upload(I.lits.empty() ? std::vector<int32_t>{0} : I.lits, s.stream);
+    s.d_inc_offs.upload(I.offs, s.stream);
+    attach_clauses(s, 0, s.n_alloc, c0, c1);    // (without new clauses it still takes every worker to level 0)
+    HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
+    std::vector<MsState> sts;
+    gather_states(s, sts);
+    s.stats.workers = W;
+    sw.active = true;
+    for (const MsState& st : sts) {
+        if (st.status == MS_ST_ERR_INTERNAL) throw HipErr{status_text(st.status)};
+        if (st.status < 0) { sw.active = false; return MI355SAT_COLD_DEVICE_FULL; }
+        if (st.status == MS_ST_UNSAT && sw.decided == 0) {      // a new clause is false under the level-0 facts
+            I.refuted = true;
+            sw.results[0] = MI355SAT_UNSAT;
+            sw.decided = 1;
+        }
+    }
+    sw.sts = sts;
+    return MI355SAT_COLD_NONE;
+}
+
 // One slice of the search kernel over all workers.  Returns 0 or a negative error.
 int sweep_step(mi355sat& s, Sweep& sw) {
     if (!sw.active) return 0;
@@ -1926,6 +2090,8 @@ int sweep_step(mi355sat& s, Sweep& sw) {
             sw.sts.resize(s.n_workers, MsState{});
             rebalance_workers(s, sw);
         }
+        // (warm incremental solve) workers fresh from the template know the uploaded formula only: everything attached since
+        if (sw.keep_warm && s.n_alloc > had && s.inc.offs.size() > 1) attach_clauses(s, had, s.n_alloc, 0, (uint32_t)(s.inc.offs.size() - 1));
     }
     // default slice length: 20 ms while a solve is young (easy bounds are decided within a few), 50 ms after one second
     // and 100 ms after ten of kernel time - the host's share per slice (collecting states, the caller's loop) was a
@@ -1970,7 +2136,7 @@ int sweep_step(mi355sat& s, Sweep& sw) {
             sw.results[inst] = MI355SAT_UNSAT; sw.winner[inst] = (int32_t)w; sw.decided++;
         }
     }
-    sw.conflicts = confl;
+    sw.conflicts = confl - sw.conflicts0;
     if (s.opts.verbose) {
         uint64_t props = 0, nl = 0, busy = 0, viv = 0, vivl = 0;
         for (auto& st : sw.sts) { props += st.propagations; nl += st.n_learnts; viv += st.n_vivified; vivl += st.n_viv_lits; }
@@ -2006,7 +2172,19 @@ void consume_interrupt(mi355sat& s) {
 }
 
 void sweep_end(mi355sat& s, Sweep& sw) {
-    if (sw.active) accumulate_stats(s, sw.sts);
+    if (sw.active && !sw.counters0.empty()) {   // a warm solve: the workers' counters ran on from the solve before
+        std::vector<MsState> d = sw.sts;
+        for (size_t w = 0; w < d.size() && w < sw.counters0.size(); w++) {
+            const MsState& b = sw.counters0[w];
+            d[w].n_steps -= b.n_steps; d[w].n_redo -= b.n_redo; d[w].propagations -= b.propagations; d[w].decisions -= b.decisions;
+            d[w].conflicts -= b.conflicts; d[w].restarts -= b.restarts; d[w].reduce_dbs -= b.reduce_dbs; d[w].n_watch -= b.n_watch;
+            d[w].n_cl_lit -= b.n_cl_lit; d[w].n_move -= b.n_move; d[w].n_enq -= b.n_enq; d[w].n_exported -= b.n_exported;
+            d[w].n_imported -= b.n_imported; d[w].n_imported_units -= b.n_imported_units; d[w].slice_cycles -= b.slice_cycles;
+            d[w].learnt_total -= b.learnt_total; d[w].learnt_lits_total -= b.learnt_lits_total;
+            for (int i = 0; i < 16; i++) d[w].prof[i] -= b.prof[i];
+        }
+        accumulate_stats(s, d);
+    } else if (sw.active) accumulate_stats(s, sw.sts);
     sw.active = false;
     consume_interrupt(s);
 }
@@ -2015,11 +2193,61 @@ void sweep_end(mi355sat& s, Sweep& sw) {
 // for the other answers)
 int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
                uint32_t n_instances, std::vector<int32_t>& results, std::vector<int32_t>& winner, bool stop_at_first,
-               std::vector<std::vector<int32_t>>* cores = nullptr) {
+               std::vector<std::vector<int32_t>>* cores = nullptr, bool plain_solve = false) {
+    mi355sat::Incremental& I = s.inc;
+    const bool incremental = plain_solve && I.on;
+    if (!incremental) {     // solve_batch, or the mode is off: today's path, and what is on the device is no solve()'s any more
+        I.resident = false;
+        I.why_not = plain_solve ? MI355SAT_COLD_FIRST : MI355SAT_COLD_OTHER_SEARCH;
+    }
+    if (incremental && I.refuted && s.proof_path.empty()) {     // the formula only grows: UNSAT with the empty core, no launch
+        results.assign(1, MI355SAT_UNSAT);
+        winner.assign(1, -1);
+        if (cores) cores->assign(1, {});
+        consume_interrupt(s);
+        I.info.warm_solves++;
+        return 0;
+    }
     Sweep sw;
     sw.cores = cores != nullptr;
-    int rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first);
+    int rc = 0;
+    const int why = incremental ? warm_begin(s, sw, assump, assump_off) : MI355SAT_COLD_FIRST;
+    if (incremental && why == MI355SAT_COLD_NONE) I.info.warm_solves++;
+    else {
+        if (incremental) {
+            I.info.cold_solves++;
+            I.info.last_cold_reason = why;
+            I.resident = false;
+            I.why_not = MI355SAT_COLD_FIRST;
+            sw.keep_warm = s.proof_path.empty() && s.opts.cube_split <= 0;
+            sw.counters0.clear();
+            sw.conflicts0 = 0;
+        }
+        rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first);
+        if (sw.keep_warm && !rc) {
+            if (s.trivially_unsat) I.refuted = true;
+            else {      // uploaded: the next solve() may start from these workers
+                I.resident = true;
+                I.n_clauses = s.offs.size() - 1;
+                I.eliminated.assign(s.n_vars, 0);
+                for (const MsElim& e : s.elims) I.eliminated[e.x >> 1] = 1;
+                I.lits.clear();
+                I.offs.assign(1, 0);
+                I.pinned = I.pinned_lits = 0;
+            }
+        }
+    }
+    if (incremental && why == MI355SAT_COLD_NONE) sw.keep_warm = true;
+    const bool searched = sw.active;
     while (!rc && !sweep_finished(s, sw)) rc = sweep_step(s, sw);
+    if (sw.keep_warm) {
+        if (rc) { I.resident = false; I.why_not = MI355SAT_COLD_FIRST; }
+        else if (searched) {
+            I.base = sw.sts;    // (empty: interrupted before the first slice - the workers are as the template left them)
+            I.base.resize(s.n_workers, MsState{});
+            for (const MsState& st : sw.sts) if (st.status == MS_ST_UNSAT) I.refuted = true;
+        }
+    }
     sweep_end(s, sw);
     results = sw.results;
     winner = sw.winner;
@@ -2109,6 +2337,7 @@ void mi355sat_free(mi355sat* s) {
     s->d_template.release(); s->d_slabs.release(); s->d_states.release(); s->d_any_done.release();
     s->d_proof.release(); s->d_proof_len.release();
     s->d_assump.release(); s->d_script.release(); s->d_assump_off.release(); s->d_script_off.release();
+    s->d_inc_lits.release(); s->d_inc_offs.release();
     if (s->stop_flag) (void)hipHostFree(s->stop_flag);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -2215,6 +2444,20 @@ int mi355sat_set_proof_path(mi355sat* s, const char* path) {
     return 0;
 }
 
+int mi355sat_set_incremental(mi355sat* s, int on) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->inc.on = on != 0;
+    if (!s->inc.on) { s->inc.resident = false; s->inc.why_not = MI355SAT_COLD_FIRST; }
+    return 0;
+}
+
+int mi355sat_debug_incremental(const mi355sat* s, mi355sat_incremental_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    *out = s->inc.info;
+    out->enabled = s->inc.on ? 1 : 0;
+    return 0;
+}
+
 int mi355sat_solve(mi355sat* s) {
     if (!s) return MI355SAT_ERR_ARG;
     std::vector<int32_t> assump;
@@ -2229,7 +2472,7 @@ int mi355sat_solve(mi355sat* s) {
         std::vector<uint64_t> aoff{0, (uint64_t)assump.size()};
         std::vector<int32_t> results, winner;
         std::vector<std::vector<int32_t>> cores;
-        int rc = run_search(*s, assump, aoff, 1, results, winner, true, &cores);
+        int rc = run_search(*s, assump, aoff, 1, results, winner, true, &cores, /*plain_solve=*/true);
         if (rc) { proof_close(*s, false); s->stats.solve_seconds += now_s() - t0; return rc; }   // (a truncated proof file is closed, not leaked)
         result = results[0];
         if (result == MI355SAT_UNSAT) { s->core = cores[0]; s->core_valid = true; }
@@ -2238,6 +2481,8 @@ int mi355sat_solve(mi355sat* s) {
         if (result == MI355SAT_SAT) fetch_model(*s, (uint32_t)winner[0], s->model, s->max_var);
     } catch (HipErr& he) {
         proof_close(*s, false);
+        s->inc.resident = false;
+        s->inc.why_not = MI355SAT_COLD_FIRST;
         s->err = he.msg;
         s->stats.solve_seconds += now_s() - t0;
         return MI355SAT_ERR_HIP;
@@ -2298,6 +2543,8 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
     const double t0 = now_s();
     try {
         HIPCHK(hipSetDevice(s->device));
+        s->inc.resident = false;     // (the slabs become this batch's)
+        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
         Prepared P;
         prepare(*s, /*simplify=*/false, P);
         if (P.unsat) {  // contradictory unit clauses: every instance conflicts before any decision
@@ -2381,6 +2628,8 @@ int mi355sat_sweep_begin(mi355sat* s, const int32_t* assumps, const uint64_t* as
         delete s->sweep;
         s->sweep = new SweepHolder;
         s->sweep->base = s->stats;
+        s->inc.resident = false;
+        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
         return sweep_begin(*s, s->sweep->sw, assump, aoff, (uint32_t)n_instances, false);
     } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
     catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }

@@ -366,6 +366,66 @@ def solver_loop_sweep(grid, encoding, limits, make_solver=None, out=print, on_in
     return hist + rest
 
 
+def solver_loop_incremental(grid, encoding, limits, make_solver=None, out=print, on_interrupter=None, max_iterations=None):
+    """The reference's loop (main.rs:290-346: the same messages in the same order, the same `on_interrupter` contract and
+    records as solver_loop) over ONE solver handle in its warm incremental mode (`Mi355Sat.set_incremental`): one CNF with
+    the totalizer built for the first bound; every tighter bound k is a UNIT on that totalizer's output for k (the literal
+    `_sweep_below` assumes for it, here added for good: the bound only ever tightens), then solve() again - which goes on
+    with the workers of the solve before, their learnt clauses, phases (the last model) and decision order.  Only the
+    `-l1:K` form.  A first bound so loose that it needs no totalizer (or zero) leaves nothing to tighten: the next bound
+    then gets a handle and a CNF of its own, and the loop goes on from there.  Opt-in: whether a warm ladder is faster
+    than solver_loop_sweep's fresh CNF per bound is a measurement, not a given."""
+    if set(limits.card_limits) != {(1, 1)} or limits.weights or limits.weight_limit is not None:
+        raise ValueError("solver_loop_incremental handles a single 1x1 cardinality limit; use solver_loop / weight_loop")
+    make_solver = make_solver or (lambda: Mi355Sat())
+    k = limits.card_limits[(1, 1)]
+    history = []
+    solver = cnf = None
+    try:
+        while max_iterations is None or len(history) < max_iterations:
+            if solver is not None and k < len(cnf.card_outputs):
+                solver.add_clause([-int(cnf.card_outputs[k])])      # at most k  <=>  not (at least k + 1)
+            else:
+                if solver is not None:
+                    solver.close()
+                cnf = encoding.with_limits_into_cnf(PlatformLimits({(1, 1): k}), sweep=True)
+                solver = make_solver()
+                solver.set_incremental(True)
+                solver.add_cnf(cnf.lits, cnf.offsets)
+                solver.reserve(cnf.n_vars)
+            if on_interrupter:
+                on_interrupter(solver.interrupter())
+            t0 = time.perf_counter()
+            result = solver.solve()
+            dt = time.perf_counter() - t0
+            rec = {"k": k, "result": result, "count": None, "valid": None, "seconds": dt, "stats": solver.stats(),
+                   "incremental": solver.debug_incremental()}
+            history.append(rec)
+            if result == SolverResult.Unsat:
+                out("No solution found for the current constraints")
+                return history
+            if result == SolverResult.Interrupted:
+                out("Solver interrupted")
+                return history
+            layout = PlatformLayout.from_assignment(solver.full_solution(encoding.n_vars), encoding)
+            count = layout.platform_count()
+            rec["count"] = count
+            rec["layout"] = layout
+            if count == 0:
+                out("Found a solution with no platforms - aborting")
+                return history
+            k = count - 1
+            out(f"Solution found ({count} platforms total)")
+            for (w, h), n in sorted(layout.platform_stats().items()):
+                out(f"{w}x{h}: {n}")
+            rec["valid"] = layout.validate(grid).is_valid()
+            out("Solution validation OK" if rec["valid"] else "Solution validation FAILED")
+        return history
+    finally:
+        if solver is not None:
+            solver.close()
+
+
 def frontier_weights(ks, res, best_c, unsat_k, rest=0.02):
     """The refinement ends when max UNSAT k + 1 == min SAT count, so two open bounds decide it: the highest (a
     model there lowers the ceiling - the reference's own next iteration, main.rs:346) and the lowest (a refutation

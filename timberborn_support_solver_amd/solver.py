@@ -70,6 +70,28 @@ class Mi355SatSearchBuild(ctypes.Structure):   # mi355sat_search_build (test hoo
         return d
 
 
+class Mi355SatIncrementalInfo(ctypes.Structure):   # mi355sat_incremental_info (test hook)
+    _fields_ = [("enabled", ctypes.c_int32), ("last_cold_reason", ctypes.c_int32)] + \
+               [(n, ctypes.c_uint64) for n in ("warm_solves", "cold_solves", "attached_clauses", "attached_units",
+                                               "resident_learnts", "attach_launches")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
+    NONE = 0
+    FIRST = 1
+    NEW_VAR = 2
+    ELIMINATED = 3
+    PROOF = 4
+    CUBE_SPLIT = 5
+    PINNED_SHARE = 6
+    OTHER_SEARCH = 7
+    ASSUMP_CAP = 8
+    DEVICE_FULL = 9
+
+
 def algorithmic_bytes(stats):
     """12*n_deq + 9*n_watch + 5*n_cl_lit + 8*n_move + 13*n_enq."""
     return (12 * stats["n_deq"] + 9 * stats["n_watch"] + 5 * stats["n_cl_lit"] + 8 * stats["n_move"]
@@ -117,6 +139,8 @@ def _bind(L):
     L.mi355sat_debug_last_search_build.argtypes = [vp, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_debug_search_build_rule.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
+    L.mi355sat_set_incremental.argtypes = [vp, ctypes.c_int]
+    L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_share_export.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_share_import.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     return L
@@ -362,6 +386,20 @@ class Mi355Sat:
         """DRUP proof of the next plain solve(), in its default configuration: all workers, clause exchange on (one log per
         worker, drained after every slice)."""
         self._check(self._L.mi355sat_set_proof_path(self._h, path.encode() if path else None), "set_proof_path")
+
+    def set_incremental(self, on=True):
+        """Warm incremental solve: with it on, a solve() after clauses and / or assumptions were added goes on with the
+        workers of the solve before - their learnt clauses, saved phases and decision order - instead of preparing the
+        formula from scratch; where that is not possible it silently starts cold (include/mi355sat.h lists when).
+        reserve() the variables of later clauses before the first solve."""
+        self._check(self._L.mi355sat_set_incremental(self._h, 1 if on else 0), "set_incremental")
+
+    def debug_incremental(self):
+        """Test hook: warm / cold solves so far, clauses and units attached warm, learnt clauses resident when the last
+        warm solve began, reason (ColdReason) of the last cold start."""
+        info = Mi355SatIncrementalInfo()
+        self._check(self._L.mi355sat_debug_incremental(self._h, ctypes.byref(info)), "debug_incremental")
+        return info.as_dict()
 
     def lit_val(self, lit):
         return self._L.mi355sat_val(self._h, int(lit))
