@@ -348,6 +348,21 @@ typedef struct mi355sat_incremental_info {
 } mi355sat_incremental_info;
 int mi355sat_debug_incremental(const mi355sat* s, mi355sat_incremental_info* out);
 
+/* Test hook: what the optional heuristics did, summed over the workers of the last solve / batch / sweep. */
+typedef struct mi355sat_heuristics_info {
+    uint64_t n_vivified;           /* opts.vivify: learnt clauses a vivification pass shortened */
+    uint64_t n_viv_lits;           /*              literals it removed from them */
+    uint64_t n_rephase;            /* opts.rephase: times a worker reset its saved phases to its best assignment */
+    uint64_t import_skipped;       /* opts.import_pct: exchanged records of three and more literals a worker passed over */
+    uint64_t forced_imports;       /* opts.share_interval: imports for which a worker gave up its search path (backtracked
+                                    * to level 0 in mid-search) */
+} mi355sat_heuristics_info;
+int mi355sat_debug_heuristics(const mi355sat* s, mi355sat_heuristics_info* out);
+/* Test hook: when the optional heuristics run, in conflicts of one worker: the first vivification pass (default 1500) and
+ * the distance between passes (400); the first rephasing, the n-th one following n + 1 times as long after its
+ * predecessor (2000).  0 keeps the default; the two periods are at most 65535.  Takes effect with the next solve. */
+int mi355sat_debug_set_schedule(mi355sat* s, uint32_t first_vivify, uint32_t vivify_every, uint32_t rephase_every);
+
 /* Clause exchange BETWEEN handles that search the SAME formula - the replicas of the sharded loop's last bounds, one
  * handle per GPU (every rank poses the reference's next bound, crates/repl/src/main.rs:292-295, with its own
  * seed).  Inside one handle the workers pass their short / low-LBD learnt clauses on through a ring on the device;

@@ -137,6 +137,48 @@ def assert_search_build(solver, lds, wps):
     return b
 
 
+def random_cnf(seed, n_vars, n_clauses, lens=(3,)):
+    """Uniform random k-SAT as a list of clauses (DIMACS literals): every clause draws its length from `lens` (no draw when
+    there is one length only), then that many distinct variables and a fair sign for each."""
+    rng = np.random.default_rng(seed)
+    cl = []
+    for _ in range(n_clauses):
+        k = lens[0] if len(lens) == 1 else int(rng.choice(lens))
+        vs = rng.choice(n_vars, size=k, replace=False)
+        cl.append([int(v + 1) * (1 if rng.random() < 0.5 else -1) for v in vs])
+    return cl
+
+
+def salt_cnf(clauses, seed, n_vars, n_each=6, n_units=3):
+    """The same formula made awkward for a clause loader: `n_each` exact duplicates, clauses with one literal repeated,
+    permuted duplicates, tautologies (x and -x in one clause: they constrain nothing) and `n_units` unit clauses, shuffled in
+    among the others."""
+    rng = np.random.default_rng(seed)
+    out = [list(c) for c in clauses]
+    pick = lambda: list(out[int(rng.integers(len(clauses)))])
+    extra = []
+    for _ in range(n_each):
+        extra.append(pick())                                        # duplicate
+        c = pick(); c.insert(int(rng.integers(len(c) + 1)), c[int(rng.integers(len(c)))]); extra.append(c)   # repeated literal
+        c = pick(); extra.append([c[i] for i in rng.permutation(len(c))])                                     # permuted duplicate
+        c = pick(); c.insert(int(rng.integers(len(c) + 1)), -c[int(rng.integers(len(c)))]); extra.append(c)  # tautology
+        v = int(rng.integers(n_vars)) + 1; extra.append([v, -v])                                              # binary tautology
+    for _ in range(n_units):
+        extra.append([(int(rng.integers(n_vars)) + 1) * (1 if rng.random() < 0.5 else -1)])
+    for c in extra:
+        out.insert(int(rng.integers(len(out) + 1)), c)
+    return out
+
+
+class Csr:
+    """A clause list in the shape the tests pass around (like the encoder's Cnf: lits, offsets, n_vars, n_clauses)."""
+
+    def __init__(self, clauses, n_vars):
+        from oracle import oracle as ora
+        self.clauses, self.n_vars, self.n_clauses = clauses, n_vars, len(clauses)
+        self.lits, self.offsets = ora.to_csr(clauses)
+
+
 def long_list_formula(seed, n_vars=360, n_long=140, n_hubs=6, per_hub=44, hub_len=(9, 40)):
     """A formula cut for the BCP step's side paths: clauses of 10..48 literals (tails to scan, several per step), a few
     hub literals watched by 44 long clauses each (watch lists far longer than a lane group: the flat remainder, its

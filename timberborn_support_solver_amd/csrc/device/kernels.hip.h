@@ -1230,6 +1230,11 @@ DEV void analyze_visit_clause(Wk& w, const MsShared& sh, const MsLayout& L, Gp<M
 // inside the chunk is picked up by the next round.  Once the chunk holds every open literal, the walk is sequential
 // (the last open one is the UIP and must not be resolved).  Round 2 resolved one literal per iteration (~160 per
 // conflict at ~1 us each).  Returns the UIP literal, or -1 (internal error).
+// A resolved literal KEEPS its mark until the walk leaves its chunk (`done` says which lanes' literals are resolved): a
+// batched round resolves literals that lie BELOW others that are still to come, whose reasons may name them.  With the
+// mark gone such a literal was marked, counted, appended to `toclear` and resolved a second time - the same clause in
+// the end, but `toclear` has room for every variable ONCE: on a short trail with dense reasons (random 3-SAT, 120
+// variables) it ran over into the arrays behind it.  Below the chunk no reason can name what lies in it.
 template <bool LV>
 DEV int analyze_walk(Wk& w, const MsShared& sh, const MsLayout& L, Gp<MsVarRec> vrec, Gp<int32_t> toclear, Gp<int32_t> learnt_buf,
                          Gp<uint32_t> lc_lbd, int dl, int& path_c, int& n_out, int& n_clear) {
@@ -1241,20 +1246,24 @@ DEV int analyze_walk(Wk& w, const MsShared& sh, const MsLayout& L, Gp<MsVarRec> 
         const int my = pos >= 0 ? WKA(int32_t, trail)[pos] : 0;
         const int myv = my >> 1;
         bool have = false;          // this lane's record and reason head are in registers
+        bool done = false;          // this lane's literal is resolved; its mark stands until the chunk is left
         MsVarRec rec = MsVarRec{0, MS_REASON_NONE, 0, 0, 0, 0};
         int4 l0 = make_int4(0, 0, 0, 0), l1 = make_int4(0, 0, 0, 0);
         for (;;) {
             lds_fence();
             bool mine;
-            if (LV) mine = pos >= 0 && pos <= index && ((w.lseen[myv >> 5] >> (myv & 31)) & 1u);
+            if (LV) mine = !done && pos >= 0 && pos <= index && ((w.lseen[myv >> 5] >> (myv & 31)) & 1u);
             else {      // marks in the records: every lane of the chunk still in play re-reads its own (one round trip per round)
                 wave_fence();
-                const bool inr = pos >= 0 && pos <= index;
+                const bool inr = !done && pos >= 0 && pos <= index;
                 if (inr) rec = vrec[myv];
                 mine = inr && rec.seen;
             }
             const u64 sm = ballot(mine);
-            if (sm == 0) break;
+            if (sm == 0) {
+                if (done) seen_clr<LV>(w, sh, L, myv);
+                break;
+            }
             const int cnt = popc64(sm);
             if (mine && !have) {    // records, then reason heads, of every marked literal of the chunk not fetched yet
                 if (LV) rec = vrec[myv];
@@ -1281,7 +1290,7 @@ DEV int analyze_walk(Wk& w, const MsShared& sh, const MsLayout& L, Gp<MsVarRec> 
                 index = chunk_hi - f - 1;
                 path_c--;
                 if (path_c <= 0) {      // the first UIP: not resolved
-                    if (me) seen_clr<LV>(w, sh, L, myv);
+                    if (me || done) seen_clr<LV>(w, sh, L, myv);
                     lds_fence();
                     wave_fence();
                     return bcast(my, f);
@@ -1316,11 +1325,10 @@ DEV int analyze_walk(Wk& w, const MsShared& sh, const MsLayout& L, Gp<MsVarRec> 
                 else clause_range(w, sh, L, cref, cl, size);
                 analyze_visit_clause<LV>(w, sh, L, vrec, toclear, learnt_buf, cl, size, bcast(myv, fb), dl, path_c, n_out, n_clear);
             }
-            // the resolved literals' own marks go LAST: while they stand, no reason of this round can mark them anew
-            lds_fence();
-            wave_fence();
-            if (me) seen_clr<LV>(w, sh, L, myv);
+            if (me) done = true;
         }
+        lds_fence();
+        wave_fence();
         index = chunk_hi - MS_WAVE;     // nothing marked is left in this chunk at or below `index`
     }
 }
@@ -1937,6 +1945,7 @@ struct LoopState {
     bool rephase;
     uint32_t import_pct;
     uint32_t vivify;           // clauses per vivification pass (0 = off)
+    uint32_t sched;            // MsParams::sched
     u64 next_vivify, n_vivified, n_viv_lits;
     double restart_k;          // Glucose's K: restart when the recent LBD average times K exceeds the global one
 };
@@ -1985,7 +1994,7 @@ DEV void ls_uniformize(LoopState& ls) {
     ls.best_trail = uni(ls.best_trail); ls.n_rephase = (uint32_t)uni((int)ls.n_rephase); ls.next_rephase = uni64(ls.next_rephase);
     ls.rephase = uni((int)ls.rephase) != 0;
     ls.import_pct = (uint32_t)uni((int)ls.import_pct);
-    ls.vivify = (uint32_t)uni((int)ls.vivify); ls.next_vivify = uni64(ls.next_vivify); ls.n_vivified = uni64(ls.n_vivified); ls.n_viv_lits = uni64(ls.n_viv_lits);
+    ls.vivify = (uint32_t)uni((int)ls.vivify); ls.sched = (uint32_t)uni((int)ls.sched); ls.next_vivify = uni64(ls.next_vivify); ls.n_vivified = uni64(ls.n_vivified); ls.n_viv_lits = uni64(ls.n_viv_lits);
     ls.restart_k = __longlong_as_double((long long)uni64((u64)__double_as_longlong(ls.restart_k)));
 }
 
@@ -2002,6 +2011,7 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
     Gp<int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
     Gp<const int32_t> pool = (Gp<const int32_t>)ls.share_pool;
     int budget = 4096;   // records per call; the rest waits for the next restart
+    uint32_t skipped = 0;
     for (; pos < end && budget > 0 && w.status == MS_ST_RUNNING; pos++, budget--) {
         // one record per step, one literal per lane (records are 128 bytes: one coalesced load)
         const int word = pool[(pos % ls.share_slots) * MS_SHARE_REC + (u64)(w.lane & (MS_SHARE_REC - 1))];
@@ -2009,7 +2019,7 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
         const int rn = hdr & 63, rl = (hdr >> 6) & 255;
         if ((uint32_t)(hdr >> 14) == ls.wid || rn < 1 || rn > MS_SHARE_MAXLEN) continue;
         // import_pct < 100: a worker attaches only that share of the clauses of 3 and more literals (each worker another one)
-        if (rn > 2 && ls.import_pct < 100 && (uint32_t)((((uint32_t)pos * 2654435761u) ^ (ls.wid * 40503u)) >> 13) % 100u >= ls.import_pct) continue;
+        if (rn > 2 && ls.import_pct < 100 && (uint32_t)((((uint32_t)pos * 2654435761u) ^ (ls.wid * 40503u)) >> 13) % 100u >= ls.import_pct) { skipped++; continue; }
         const bool in = w.lane >= 1 && w.lane <= rn;
         const int v = in ? lit_value<LV>(w, sh, L, word) : MS_VAL_FALSE;   // units attached before are visible
         if (ballot(in && v == MS_VAL_TRUE)) continue;
@@ -2029,6 +2039,7 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
         ls.n_imported++;
     }
     ls.share_pos = pos;
+    if (skipped && w.lane == 0) WK_PTR(MsState, w, L, state)->n_import_skipped += skipped;
 }
 
 // A conflict was found by propagate(): learn, backjump, assert (Glucose `search` conflict branch).
@@ -2248,13 +2259,13 @@ DEV void on_fixpoint_body(Wk& w, const MsShared& sh, const MsLayout& L, LoopStat
                 if (b != 255) VREC[v].phase = b;
             }
             ls.n_rephase++;
-            ls.next_rephase = ls.conflicts + 2000ull * (ls.n_rephase + 1);
+            ls.next_rephase = ls.conflicts + (u64)((ls.sched >> 16) ? (ls.sched >> 16) : 2000u) * (ls.n_rephase + 1);
             ls.best_trail = 0;      // the next era records its own best
             wave_fence();
         }
     }
     if (VIV && ls.vivify && w.n_levels == 0 && ls.conflicts >= ls.next_vivify) {
-        ls.next_vivify = ls.conflicts + 400;
+        ls.next_vivify = ls.conflicts + ((ls.sched & 0xffffu) ? (ls.sched & 0xffffu) : 400u);
         if (vivify_pass<LV>(w, sh, L, ls)) rebuild_watches(w, sh, L);   // shrunk clauses watch their new first two literals
         if (w.status != MS_ST_RUNNING || w.qhead < w.trail_n) return;   // a new unit: BCP first
     }
@@ -2269,7 +2280,10 @@ DEV void on_fixpoint_body(Wk& w, const MsShared& sh, const MsLayout& L, LoopStat
     if (w.status != MS_ST_RUNNING) return;
     if (ls.share_pool && ls.share_n > ls.share_pos &&
         (w.n_levels == 0 || ls.conflicts - ls.last_import_confl >= ls.share_interval)) {
-        if (w.n_levels > 0) cancel_until<LV>(w, sh, L, 0);   // other workers' clauses are waiting: take them at level 0
+        if (w.n_levels > 0) {   // other workers' clauses are waiting: take them at level 0
+            cancel_until<LV>(w, sh, L, 0);
+            if (w.lane == 0) WK_PTR(MsState, w, L, state)->n_forced_imports++;
+        }
         import_shared<LV>(w, sh, L, ls);
         ls.last_import_confl = ls.conflicts;
         if (w.status != MS_ST_RUNNING || w.qhead < w.trail_n) return;   // imported units: BCP first
@@ -2373,6 +2387,7 @@ __global__ __launch_bounds__(MS_WAVE, WPS) void ms_search_kernel(MsShared sh, Ms
     ls.rephase = prm.rephase == 1 || (prm.rephase == 2 && (wid & 1u));
     ls.import_pct = prm.import_pct > 0 ? (uint32_t)prm.import_pct : 50u;
     ls.vivify = prm.vivify > 0 ? (uint32_t)prm.vivify : 0u;      // (off by default since round 3)
+    ls.sched = prm.sched;
     ls.next_vivify = st->next_vivify; ls.n_vivified = st->n_vivified; ls.n_viv_lits = st->n_viv_lits;
     // restart_k2_pct: every second worker uses this K instead (a portfolio of restart policies)
     ls.restart_k = 0.01 * (double)(((wid & 1u) && prm.restart_k2_pct > 0) ? prm.restart_k2_pct : (prm.restart_k_pct > 0 ? prm.restart_k_pct : 100));

@@ -177,6 +177,9 @@ struct MsState {
     uint64_t next_rephase;
     // vivification
     uint64_t next_vivify, n_vivified, n_viv_lits;
+    // test-hook counters (mi355sat_debug_heuristics): exchanged records passed over by import_pct; imports that
+    // share_interval forced above level 0 (a cancel_until(0) in mid-search)
+    uint64_t n_import_skipped, n_forced_imports;
 };
 
 // Launch parameters of one slice.
@@ -205,6 +208,8 @@ struct MsParams {
     int32_t rephase;               // 0: off, 1: every worker rephases to its best assignment, 2: workers with an odd index
     int32_t restart_k_pct;         // Glucose restart factor K in percent (0 = 100)
     int32_t restart_k2_pct;        // > 0: workers with an odd index use this K
-    int32_t vivify, pad5;          // learnt clauses vivified per pass (0 / -1 = off)
+    int32_t vivify;                // learnt clauses vivified per pass (0 / -1 = off)
+    uint32_t sched;                // test hook (mi355sat_debug_set_schedule): conflicts between vivification passes in the low
+                                   // 16 bits, rephasing period in the high 16; a zero half = 400 / 2000
     int32_t import_pct;            // share (percent) of the exchanged clauses of >= 3 literals a worker attaches (0 = 50)
 };

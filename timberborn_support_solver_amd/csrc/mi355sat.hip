@@ -401,6 +401,9 @@ struct mi355sat {
     } inc;
     DevBuf<int32_t> d_inc_lits;
     DevBuf<uint32_t> d_inc_offs;
+    // test hooks: the optional heuristics' counters over the workers of the last solve; their schedule (0 = the defaults)
+    mi355sat_heuristics_info heur{};
+    uint32_t first_vivify = 0, vivify_every = 0, rephase_every = 0;
 };
 
 namespace {
@@ -747,8 +750,8 @@ void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_c
     st->pool_top = (uint32_t)pool_need;
     s.pool_init = pool_need;
     st->next_reduce = s.opts.reduce_first > 0 ? (uint64_t)s.opts.reduce_first : 2000;
-    st->next_rephase = 2000;
-    st->next_vivify = 1500;   // (easy bounds are decided before that: vivification is for the long refutations)
+    st->next_rephase = s.rephase_every ? s.rephase_every : 2000;
+    st->next_vivify = s.first_vivify ? s.first_vivify : 1500;   // (easy bounds are decided before that: vivification is for the long refutations)
     memset(T + L.best, 255, nv);
     uint8_t* val = (uint8_t*)(T + L.val);        // zero = every variable unassigned
     MsVarRec* vrec = (MsVarRec*)(T + L.vrec);
@@ -1380,6 +1383,11 @@ void accumulate_stats(mi355sat& s, const std::vector<MsState>& sts) {
     uint64_t exported = 0, imported = 0, imported_units = 0;
     for (auto& st : sts) { exported += st.n_exported; imported += st.n_imported; imported_units += st.n_imported_units; }
     o.shared_exported += exported; o.shared_imported += imported; o.shared_imported_units += imported_units;
+    s.heur = mi355sat_heuristics_info{};
+    for (auto& st : sts) {
+        s.heur.n_vivified += st.n_vivified; s.heur.n_viv_lits += st.n_viv_lits; s.heur.n_rephase += st.n_rephase;
+        s.heur.import_skipped += st.n_import_skipped; s.heur.forced_imports += st.n_forced_imports;
+    }
     uint64_t prof[16] = {0}, cyc = 0;
     for (auto& st : sts) { for (int i = 0; i < 16; i++) prof[i] += st.prof[i]; cyc += st.slice_cycles; }
     if (prof[0] && s.opts.verbose) {
@@ -1471,6 +1479,7 @@ SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_r
     prm.restart_k2_pct = s.opts.restart_k2_pct;
     prm.import_pct = s.opts.import_pct;
     prm.vivify = s.opts.vivify;
+    prm.sched = s.vivify_every | (s.rephase_every << 16);
     const bool share = mode == 0 && s.share_slots != 0;
     const uint32_t share_intake_cap = (uint32_t)std::max(16, slice_ms > 0 ? 16 * slice_ms : 256);   // 16 clauses per ms of slice
     if (share) {
@@ -2181,6 +2190,8 @@ void sweep_end(mi355sat& s, Sweep& sw) {
             d[w].n_cl_lit -= b.n_cl_lit; d[w].n_move -= b.n_move; d[w].n_enq -= b.n_enq; d[w].n_exported -= b.n_exported;
             d[w].n_imported -= b.n_imported; d[w].n_imported_units -= b.n_imported_units; d[w].slice_cycles -= b.slice_cycles;
             d[w].learnt_total -= b.learnt_total; d[w].learnt_lits_total -= b.learnt_lits_total;
+            d[w].n_vivified -= b.n_vivified; d[w].n_viv_lits -= b.n_viv_lits; d[w].n_rephase -= b.n_rephase;
+            d[w].n_import_skipped -= b.n_import_skipped; d[w].n_forced_imports -= b.n_forced_imports;
             for (int i = 0; i < 16; i++) d[w].prof[i] -= b.prof[i];
         }
         accumulate_stats(s, d);
@@ -2455,6 +2466,20 @@ int mi355sat_debug_incremental(const mi355sat* s, mi355sat_incremental_info* out
     if (!s || !out) return MI355SAT_ERR_ARG;
     *out = s->inc.info;
     out->enabled = s->inc.on ? 1 : 0;
+    return 0;
+}
+
+int mi355sat_debug_heuristics(const mi355sat* s, mi355sat_heuristics_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    *out = s->heur;
+    return 0;
+}
+
+int mi355sat_debug_set_schedule(mi355sat* s, uint32_t first_vivify, uint32_t vivify_every, uint32_t rephase_every) {
+    if (!s || vivify_every > 0xffffu || rephase_every > 0xffffu) return MI355SAT_ERR_ARG;
+    s->first_vivify = first_vivify; s->vivify_every = vivify_every; s->rephase_every = rephase_every;
+    s->inc.resident = false;      // next_vivify / next_rephase are part of a worker's state: the next solve starts cold
+    s->inc.why_not = MI355SAT_COLD_FIRST;
     return 0;
 }
 

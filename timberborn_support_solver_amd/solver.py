@@ -79,6 +79,13 @@ class Mi355SatIncrementalInfo(ctypes.Structure):   # mi355sat_incremental_info (
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatHeuristicsInfo(ctypes.Structure):   # mi355sat_heuristics_info (test hook)
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_vivified", "n_viv_lits", "n_rephase", "import_skipped", "forced_imports")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
     NONE = 0
     FIRST = 1
@@ -141,6 +148,8 @@ def _bind(L):
                                                    ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_set_incremental.argtypes = [vp, ctypes.c_int]
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
+    L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
+    L.mi355sat_debug_set_schedule.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
     L.mi355sat_share_export.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_share_import.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     return L
@@ -400,6 +409,19 @@ class Mi355Sat:
         info = Mi355SatIncrementalInfo()
         self._check(self._L.mi355sat_debug_incremental(self._h, ctypes.byref(info)), "debug_incremental")
         return info.as_dict()
+
+    def debug_heuristics(self):
+        """Test hook: what the optional heuristics did, summed over the workers of the last solve: clauses vivified and
+        literals removed from them, rephasings, exchanged records skipped by import_pct, imports that share_interval forced
+        above level 0."""
+        info = Mi355SatHeuristicsInfo()
+        self._check(self._L.mi355sat_debug_heuristics(self._h, ctypes.byref(info)), "debug_heuristics")
+        return info.as_dict()
+
+    def debug_set_schedule(self, first_vivify=0, vivify_every=0, rephase_every=0):
+        """Test hook: conflicts of one worker before its first vivification pass, between passes, and before its first
+        rephasing (0 = the defaults 1500 / 400 / 2000), from the next solve on."""
+        self._check(self._L.mi355sat_debug_set_schedule(self._h, first_vivify, vivify_every, rephase_every), "debug_set_schedule")
 
     def lit_val(self, lit):
         return self._L.mi355sat_val(self._h, int(lit))
