@@ -280,6 +280,19 @@ int mi355sat_stats(const mi355sat* s, mi355sat_stats_t* out);
  * too small. */
 int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_t* n_records);
 
+/* Test hooks: the formula the workers actually receive.  Armed (on != 0) before a solve / batch / sweep, the handle keeps
+ * a copy of what the simplification before search (opts.simp) left at that call's cold start; it costs nothing unless
+ * armed, and on = 0 drops the copy.  mi355sat_debug_simplified() hands it out as clauses of DIMACS literals in the caller's
+ * variables, each clause 0-terminated:
+ *   which 0: the remaining clauses, every level-0 fact as a one-literal clause, both binary clauses of every
+ *            substitution by an equivalent literal - and the empty clause (a lone 0) if the simplification refuted the formula;
+ *   which 1: the clauses kept aside for the eliminated variables (opts.simp = 2), from which a model gets their values.
+ * Every clause of both lists is a consequence of the caller's formula; without elimination list 0 is equivalent to it -
+ * tests/ prove both with the oracle.  out may be NULL to size the buffer; *n_words receives the length in words,
+ * *n_clauses the number of clauses.  MI355SAT_ERR_ARG if cap_words is too small, MI355SAT_ERR_STATE if nothing was kept. */
+int mi355sat_debug_keep_simplified(mi355sat* s, int on);
+int mi355sat_debug_simplified(mi355sat* s, int which, int32_t* out, uint64_t cap_words, uint64_t* n_words, uint64_t* n_clauses);
+
 /* Test hooks: which build of the search kernel a launch runs.  ms_search_kernel<LV, WPS> exists in six builds (assignment
  * staged in LDS or left in the worker's slab; compiled for 1, 2 or 4 waves per SIMD) and every launch picks one from the
  * number of workers it runs, opts.one_per_simd, opts.lds_val and an LDS budget (150 KB per CU shared by the launch's

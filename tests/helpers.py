@@ -170,6 +170,145 @@ def salt_cnf(clauses, seed, n_vars, n_each=6, n_units=3):
     return out
 
 
+STRUCTURE = ("equiv", "failed", "subsume", "strengthen", "long", "elim", "salt")
+
+
+def structured_cnf(seed, n_vars, n_clauses, lens=(2, 3, 4, 5, 6), features=STRUCTURE, refute=None, glue=0.5):
+    """A random_cnf base of n_clauses over the variables 1..n_base (mixed lengths, below the threshold) with the structure planted that
+    the simplification before search lives on and uniform random k-SAT does not have.  Every feature is a switch (`features`,
+    names of STRUCTURE), so that a case can isolate one:
+      equiv       binary implication cycles of 2..5 literals with mixed signs; two cycles joined by a later binary clause; a
+                  cycle whose representative a mutual pair then fixes; and - with "elim" - cycles whose representative is cheap
+                  to eliminate, the other member sitting in a clause of its own
+      failed      l -> a, l -> b, (~a | ~b) through binary and through ternary clauses; a -> m and ~a -> m; a -> m and
+                  ~a -> ~m, both through paths that are not binary clauses
+      subsume     supersets of existing clauses, exact and permuted duplicates
+      strengthen  pairs (C | x), (D | ~x) with C inside D; a clause two others strengthen on different literals in one pass;
+                  a strengthening that leaves a binary; the mutual pair (a | b), (a | ~b); all four sign patterns of (x, y)
+                  next to a literal a (two passes of strengthening leave the unit a; unit propagation does not find it)
+      long        a clause of 70 literals with a superset (too long to subsume: both stay) and a clause of 66 literals with a
+                  binary subsumer
+      elim        variables with 1..3 occurrences per polarity, pure literals, the gates x = a & b and x = a | b, all sixteen
+                  sign patterns of four variables next to a literal (three passes of strengthening leave (x | a), (~x | a):
+                  eliminating x makes the unit resolvent a)
+      salt        salt_cnf: duplicates, repeated literals, tautologies, units
+    The gadgets' own variables are n_base+1 .. n_vars (n_base = n_vars minus what the chosen gadgets need), their side literals
+    come from the base, and `glue` * (number of gadget variables) random ternary clauses tie gadget variables to base variables.
+    refute = "scc" puts x and ~x into one implication component, "failed" makes a literal fail in both polarities (through
+    ternary clauses): the planted structure alone refutes the formula.
+    Returns (clauses, special): special = the gadgets' variables - substituted, fixed or eliminated ones among them."""
+    rng = np.random.default_rng(seed)
+    need = {"equiv": 18 + (8 if "elim" in features else 0), "failed": 15, "strengthen": 9, "long": 72, "elim": 13}
+    n_own = sum(need.get(f, 0) for f in features) + {None: 0, "scc": 3, "failed": 5}[refute]
+    n_base = n_vars - n_own
+    assert n_base >= 12, "structured_cnf: n_vars leaves too few variables for the base"
+    cl = random_cnf(seed, n_base, n_clauses, lens)
+    nxt = [n_base]
+    special = []
+
+    def fresh(k):
+        vs = list(range(nxt[0] + 1, nxt[0] + k + 1))
+        nxt[0] += k
+        assert nxt[0] <= n_vars
+        special.extend(vs)
+        return vs
+
+    def sign(v):
+        return v if rng.random() < 0.5 else -v
+
+    def base(k):                                    # k literals over distinct base variables
+        return [sign(int(v) + 1) for v in rng.choice(n_base, size=k, replace=False)]
+
+    def cycle(ls):                                  # l0 -> l1 -> ... -> l0
+        return [[-ls[i], ls[(i + 1) % len(ls)]] for i in range(len(ls))]
+
+    extra = []
+    if "equiv" in features:
+        for k in (2, 3, 4, 5):
+            ls = [sign(v) for v in fresh(k - 1)] + base(1)
+            extra += cycle([ls[i] for i in rng.permutation(k)])
+        a, b = [sign(v) for v in fresh(2)], [sign(v) for v in fresh(3)]         # two cycles, joined below
+        extra += cycle(a) + cycle(b)
+        joined = [[-a[0], b[1]], [-b[2], a[1]]]
+        r, q, x = fresh(3)                          # q == ~r, and r fixed by (r | x), (r | ~x): a failed literal, found after the cycle
+        extra += cycle([-r, q]) + [[r, x], [r, -x]] + [[-q] + base(2)]
+        if "elim" in features:
+            for _ in range(4):                      # q == +-r; after the substitution r has three occurrences
+                r, q = fresh(2)
+                s = 1 if rng.random() < 0.5 else -1
+                extra += cycle([r, s * q]) + [[r] + base(2), [-r] + base(1), [s * q] + base(2)]
+    if "failed" in features:
+        l, a, b = fresh(3)
+        extra += [[-l, a], [-l, b], [-a, -b]]
+        l, a, b, c = fresh(4)
+        extra += [[-l, a], [-l, -a, b], [-a, -b, c], [-c, -l]]
+        a, u, w, m = fresh(4)                       # a -> u, a & u -> m;  ~a -> w, ~a & w -> m
+        extra += [[-a, u], [-a, -u, m], [a, w], [a, -w, m], [-m] + base(2)]
+        a, u, w, m = fresh(4)                       # a -> u, a & u -> m;  ~a -> w, ~a & w -> ~m
+        extra += [[-a, u], [-a, -u, m], [a, w], [a, -w, -m], [m] + base(2), [-m] + base(2)]
+    if "subsume" in features:
+        for _ in range(6):
+            c = list(cl[int(rng.integers(len(cl)))])
+            more = [l for l in base(3) if abs(l) not in {abs(x) for x in c}][:int(rng.integers(1, 4))]
+            extra.append([c[i] for i in rng.permutation(len(c))] + more)
+        for _ in range(4):
+            c = cl[int(rng.integers(len(cl)))]
+            extra += [list(c), [c[i] for i in rng.permutation(len(c))]]
+    if "strengthen" in features:
+        for _ in range(3):
+            c, x = base(5), fresh(1)[0]
+            extra += [c[:2] + [x], c[:2 + int(rng.integers(0, 3))] + [-x]]
+        e = base(5)                                 # loses e[2] to the first and e[3] to the second
+        extra += [e, [e[0], e[1], -e[2]], [e[0], e[1], -e[3]]]
+        a, x = base(2)[0], fresh(1)[0]
+        extra += [[a, x], [a] + base(1) + [-x]]     # leaves a binary
+        a, b = fresh(2)
+        extra += [[a, b], [a, -b], [-a] + base(2)]  # the mutual pair
+        x, y, a = fresh(3)
+        extra += [[sx * x, sy * y, a] for sx in (1, -1) for sy in (1, -1)] + [[-a] + base(2)]
+    if "long" in features:
+        fill = fresh(72)
+        big = [sign(v) for v in fill]
+        extra += [big[:70], big]
+        a, b = base(2)
+        extra.append([a, b] + [sign(v) for v in fill[:64]])
+        extra.append([a, b])
+    if "elim" in features:
+        for n_pos, n_neg in ((1, 1), (1, 2), (2, 2), (3, 2)):
+            x = fresh(1)[0]
+            extra += [[x] + base(2) for _ in range(n_pos)] + [[-x] + base(2) for _ in range(n_neg)]
+        for _ in range(2):
+            x = sign(fresh(1)[0])
+            extra += [[x] + base(2), [x] + base(3)]                                         # pure
+        x, (a, b) = fresh(1)[0], base(2)
+        extra += [[-x, a], [-x, b], [x, -a, -b], [x] + base(2), [-x] + base(2)]              # x = a & b
+        x, (a, b) = fresh(1)[0], base(2)
+        extra += [[x, -a], [x, -b], [-x, a, b], [x] + base(2), [-x] + base(2)]               # x = a | b
+        w, x, y, z, a = fresh(5)
+        extra += [[sw * w, sx * x, sy * y, sz * z, a] for sw in (1, -1) for sx in (1, -1) for sy in (1, -1) for sz in (1, -1)]
+        extra.append([-a] + base(2))
+    if refute == "scc":
+        x, y, z = fresh(3)
+        extra += cycle([x, y, -x, z])
+    elif refute == "failed":
+        l, a, b, c, d = fresh(5)
+        extra += [[-l, a], [-l, b], [-a, -b, -l], [l, c], [l, d], [-c, -d, l]]
+    assert nxt[0] == n_vars
+    gadget_vars = list(range(n_base + 1, nxt[0] + 1))
+    if "long" in features:
+        gadget_vars = [v for v in gadget_vars if v not in fill]
+    for _ in range(int(glue * len(gadget_vars))):
+        extra.append([sign(int(rng.choice(gadget_vars)))] + base(2))
+    out = [list(c) for c in cl]
+    for c in extra:
+        out.insert(int(rng.integers(len(out) + 1)), c)
+    if "equiv" in features:
+        out += joined                               # the binary clauses that join the two cycles come last
+    if "salt" in features:
+        out = salt_cnf(out, seed + 1000, n_base, n_each=3, n_units=2)
+    return out, special
+
+
 class Csr:
     """A clause list in the shape the tests pass around (like the encoder's Cnf: lits, offsets, n_vars, n_clauses)."""
 

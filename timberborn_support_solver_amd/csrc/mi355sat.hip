@@ -404,6 +404,11 @@ struct mi355sat {
     // test hooks: the optional heuristics' counters over the workers of the last solve; their schedule (0 = the defaults)
     mi355sat_heuristics_info heur{};
     uint32_t first_vivify = 0, vivify_every = 0, rephase_every = 0;
+    // test hook (mi355sat_debug_keep_simplified): what simplify_formula left at the last cold start, as 0-terminated clauses
+    // of DIMACS literals in the caller's variables; [0] the formula the workers get, [1] the kept sides of the eliminations
+    bool keep_simplified = false, kept_valid = false;
+    std::vector<int32_t> kept[2];
+    uint64_t kept_n[2] = {0, 0};
 };
 
 namespace {
@@ -1366,6 +1371,33 @@ void simplify_formula(mi355sat& s, Formula& F) {
                 (unsigned long long)F.n_subsumed, (unsigned long long)F.n_strengthened, F.unsat ? " - UNSAT" : "");
 }
 
+// Test hook (mi355sat_debug_keep_simplified): the formula as simplify_formula left it, in the caller's variables - the
+// remaining clauses, every level-0 fact as a one-literal clause, both binary clauses of every substitution (the empty
+// clause if the simplification refuted the formula); and the clauses kept aside for the eliminated variables.
+void keep_simplified_copy(mi355sat& s, const Formula& F) {
+    auto dimacs = [](int32_t l) { return (l & 1) ? -((l >> 1) + 1) : ((l >> 1) + 1); };
+    for (int k = 0; k < 2; k++) { s.kept[k].clear(); s.kept_n[k] = 0; }
+    std::vector<int32_t>& out = s.kept[0];
+    for (size_t c = 0; c < F.n_clauses(); c++) {
+        for (uint64_t k = F.no[c]; k < F.no[c + 1]; k++) out.push_back(dimacs(F.nl[k]));
+        out.push_back(0);
+    }
+    s.kept_n[0] = F.n_clauses();
+    for (int32_t u : F.units) { out.push_back(dimacs(u)); out.push_back(0); s.kept_n[0]++; }
+    for (uint32_t v = 0; v < F.nv; v++) {
+        const int32_t r = F.subst[v];
+        if (r == 2 * (int32_t)v) continue;
+        out.insert(out.end(), {-(int32_t)(v + 1), dimacs(r), 0, (int32_t)(v + 1), dimacs(r ^ 1), 0});
+        s.kept_n[0] += 2;
+    }
+    if (F.unsat) { out.push_back(0); s.kept_n[0]++; }
+    for (int32_t l : F.elim_lits) {
+        s.kept[1].push_back(l < 0 ? 0 : dimacs(l));
+        if (l < 0) s.kept_n[1]++;
+    }
+    s.kept_valid = true;
+}
+
 void accumulate_stats(mi355sat& s, const std::vector<MsState>& sts) {
     mi355sat_stats_t& o = s.stats;
     uint64_t learnts = 0, llits = 0;
@@ -1675,6 +1707,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         for (int32_t d : assump)
             if (d != 0 && (uint64_t)(d < 0 ? -(int64_t)d : d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
         simplify_formula(s, F);
+        if (s.keep_simplified) keep_simplified_copy(s, F);
         build_csr(s, F, /*units_propagated=*/true, P);
         s.subst = F.subst;
         s.elims.swap(F.elims);
@@ -2831,6 +2864,26 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
         return w <= cap_words || !out ? 0 : MI355SAT_ERR_ARG;
     } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
     catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+}
+
+int mi355sat_debug_keep_simplified(mi355sat* s, int on) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->keep_simplified = on != 0;
+    if (!on) { for (int k = 0; k < 2; k++) { std::vector<int32_t>().swap(s->kept[k]); s->kept_n[k] = 0; } s->kept_valid = false; }
+    return 0;
+}
+
+int mi355sat_debug_simplified(mi355sat* s, int which, int32_t* out, uint64_t cap_words, uint64_t* n_words, uint64_t* n_clauses) {
+    if (!s || !n_words || !n_clauses || which < 0 || which > 1) return MI355SAT_ERR_ARG;
+    *n_words = *n_clauses = 0;
+    if (!s->kept_valid) { s->err = "no simplified formula kept: arm mi355sat_debug_keep_simplified() before the solve"; return MI355SAT_ERR_STATE; }
+    const std::vector<int32_t>& k = s->kept[which];
+    *n_words = k.size();
+    *n_clauses = s->kept_n[which];
+    if (!out) return 0;
+    if (cap_words < k.size()) return MI355SAT_ERR_ARG;
+    std::copy(k.begin(), k.end(), out);
+    return 0;
 }
 
 int mi355sat_debug_last_search_build(const mi355sat* s, mi355sat_search_build* out) {

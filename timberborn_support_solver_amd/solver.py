@@ -143,6 +143,9 @@ def _bind(L):
     L.mi355sat_stats.argtypes = [vp, ctypes.POINTER(Mi355SatStats)]
     L.mi355sat_set_proof_path.argtypes = [vp, ctypes.c_char_p]
     L.mi355sat_debug_share_ring.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_debug_keep_simplified.argtypes = [vp, ctypes.c_int]
+    L.mi355sat_debug_simplified.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_debug_last_search_build.argtypes = [vp, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_debug_search_build_rule.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
@@ -355,6 +358,31 @@ class Mi355Sat:
             else:
                 cur.append(l)
         return out
+
+    def debug_keep_simplified(self, on=True):
+        """Test hook: keep a copy of what the simplification before search leaves, from the next solve / batch on."""
+        self._check(self._L.mi355sat_debug_keep_simplified(self._h, 1 if on else 0), "debug_keep_simplified")
+
+    def debug_simplified(self):
+        """Test hook: (clauses, elim_clauses) of the last solve with debug_keep_simplified() armed, as lists of DIMACS
+        literals in the caller's variables: the formula the workers received (remaining clauses, level-0 facts as units,
+        both binaries of every substitution; the empty clause [] among them if it was refuted), and the clauses kept for the eliminated variables."""
+        lists = []
+        for which in (0, 1):
+            nw, nc = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            self._check(self._L.mi355sat_debug_simplified(self._h, which, None, 0, ctypes.byref(nw), ctypes.byref(nc)), "debug_simplified")
+            buf = np.zeros(max(nw.value, 1), dtype=np.int32)
+            self._check(self._L.mi355sat_debug_simplified(self._h, which, _p(buf), nw.value, ctypes.byref(nw), ctypes.byref(nc)), "debug_simplified")
+            out, cur = [], []
+            for l in buf[:nw.value].tolist():
+                if l == 0:
+                    out.append(cur)
+                    cur = []
+                else:
+                    cur.append(l)
+            assert not cur and len(out) == nc.value
+            lists.append(out)
+        return tuple(lists)
 
     def debug_last_search_build(self):
         """Test hook: the build of the search kernel this handle's last search launch ran, as a dict (lds 0/1, wps 1/2/4,
