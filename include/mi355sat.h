@@ -207,6 +207,57 @@ int mi355sat_core(mi355sat* s, int32_t* out, uint64_t cap, uint64_t* n);
 /* The same for instance i of the last mi355sat_solve_batch() that reported UNSAT (MI355SAT_ERR_STATE otherwise). */
 int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n);
 
+/* --- phase hints (rustsat PhaseLit's place; seeded, not forced) ------------- */
+/* A hint tells the search which polarity to try FIRST for a variable: the first time var(lit) is decided, it is decided
+ * as lit.  The refinement loop poses one bound after another to fresh solvers (crates/repl/src/main.rs:290-346) and holds
+ * a model of the bound before: hinted to it, the next solve starts its search at the last layout instead of at "no
+ * platform anywhere".  Hints stay on the handle until mi355sat_unphase() / a 0 in mi355sat_set_phases().
+ *   - A hint SEEDS the worker's saved phase; it is not forced.  Phase saving overwrites it the first time the variable is
+ *     assigned, exactly as it overwrites the FALSE default.  That is the difference from Glucose's setPolarity (rustsat
+ *     `phase_lit`), which pins the polarity of every later decision - and why this is not offered as `PhaseLit`
+ *     (INTEGRATION.md).  The search kernel is the same with and without hints.
+ *   - Hints take precedence over opts.phase_mix for the hinted variables, in every worker and replica; unhinted variables
+ *     behave exactly as without any hint.
+ *   - A variable above the highest one seen is reserved (as mi355sat_assume does).  Literal 0: MI355SAT_ERR_ARG.
+ *   - Setting or clearing a hint does not touch the IPASIR state (failed / core stay valid) and never makes an incremental
+ *     solve start cold.
+ *   - Cold start (mi355sat_solve, mi355sat_solve_batch, mi355sat_sweep_begin; not mi355sat_propagate_batch): every worker
+ *     is seeded after it got its assumptions and decision order - also the workers the ramp-up creates later.
+ *     Warm start (mi355sat_set_incremental): the resident workers are seeded only if a hint was set or changed since they
+ *     last were; a warm solve with unchanged hints launches nothing and keeps the phases the workers saved.  A cleared
+ *     hint takes nothing back: what it seeded is the worker's saved phase by then.
+ *   - A hint follows its variable through the simplification as an assumption does: through the equivalent-literal
+ *     substitution (which may flip its sign), then the device's variable order.  In increasing variable order: of two
+ *     hints that meet on one representative with opposite signs the later one wins.  A variable that opts.simp = 2
+ *     eliminated has no phase to seed (its value is computed from the others when a model is read), one fixed at level 0
+ *     none either: both hints are dropped and counted.
+ *   - The first model found is not necessarily the hinted one; but if the hints ARE a model of the formula that agrees
+ *     with the assumptions, every decision and with it every propagation agrees with it: the solve ends SAT without a
+ *     single conflict, with that model (tests/test_emu_phase.py, tests/test_gpu_phase.py).
+ *   Measured on the MI355X (profiles/r06_phase_hint_ladders.log: the plain refinement loop -l1:M, a fresh solver per bound,
+ *   every rung hinted to the model of the rung before on the encoder's variables, against the same binary without hints,
+ *   three runs each way, alternating): rect 24 2.6-3.0 s without, 1.7-1.8 s with; rect 26 10.4-11.0 s without, 10.1-10.8 s
+ *   with (within the spread: 8 of the 10 s are the last, UNSAT rung, which no hint helps); rect 28 15.5-18.3 s without,
+ *   14.1-15.5 s with.  What is gained is gained on the SAT rungs (rect 24 1.9-2.3 -> 0.9-1.2 s, rect 26 2.2-2.5 -> 1.6-2.3 s,
+ *   rect 28 6.7-9.3 -> 5.4-6.2 s); the easy ones take half the conflicts, the ones just above the optimum spread widely
+ *   either way.  Opt-in in the loops (solver_loop(phase_hints), tbs_cli --phase-hints). */
+int mi355sat_phase(mi355sat* s, int32_t lit);
+int mi355sat_unphase(mi355sat* s, int32_t var);
+/* Bulk: phases[v-1] = 1 (TRUE first) / -1 (FALSE first) / 0 (no hint; clears one) for v = 1..n_vars.  Variables above
+ * n_vars keep their hints. */
+int mi355sat_set_phases(mi355sat* s, const int8_t* phases, uint64_t n_vars);
+/* Test hook: what the hints did on this handle so far. */
+typedef struct mi355sat_phase_info {
+    uint64_t hinted;               /* variables with a hint now */
+    uint64_t applied_cold;         /* cold starts that seeded their workers (one per solve / batch / sweep with a hint set) */
+    uint64_t applied_warm;         /* warm starts that did (the hints had changed) */
+    uint64_t launches;             /* ms_phase_kernel launches so far (the ramp-up's later workers have their own) */
+    uint64_t mapped;               /* at the last application: device variables seeded in every worker, */
+    uint64_t dropped_eliminated;   /*   hints on variables that were eliminated, */
+    uint64_t dropped_fixed;        /*   hints on variables the formula fixes at level 0 */
+} mi355sat_phase_info;
+int mi355sat_debug_phases(const mi355sat* s, mi355sat_phase_info* out);
+
 /* Batched solve under assumptions: instance i = formula AND assumption literals
  * assumps[assump_offsets[i] .. assump_offsets[i+1]).  This is what the sharded
  * decreasing-k sweep uses: the clause database (base CNF + one totalizer built

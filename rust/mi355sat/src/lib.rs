@@ -13,7 +13,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 use rustsat::instances::Cnf;
 use rustsat::solvers::{Interrupt, InterruptSolver, Solve, SolveIncremental, SolveStats, SolverResult, SolverStats};
-use rustsat::types::{Cl, Clause, Lit, TernaryVal, Var};
+use rustsat::types::{Assignment, Cl, Clause, Lit, TernaryVal, Var};
 
 /// Mirror of `mi355sat_opts` (include/mi355sat.h); zero = defaults.
 #[repr(C)]
@@ -52,6 +52,9 @@ extern "C" {
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
     fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
+    fn mi355sat_phase(s: *mut c_void, lit: i32) -> c_int;
+    fn mi355sat_unphase(s: *mut c_void, var: i32) -> c_int;
+    fn mi355sat_set_phases(s: *mut c_void, phases: *const i8, n_vars: u64) -> c_int;
 }
 
 pub struct Mi355Sat { h: *mut c_void }
@@ -79,6 +82,29 @@ impl Mi355Sat {
     /// Replayed in C by tests/abi_incremental.c.
     pub fn set_incremental(&mut self, on: bool) -> anyhow::Result<()> {
         if unsafe { mi355sat_set_incremental(self.h, on as c_int) } < 0 { return Err(self.err()); }
+        Ok(())
+    }
+    /// Phase hint (`mi355sat_phase`): the first time `lit`'s variable is decided, it is decided as `lit`.  The hint SEEDS
+    /// the workers' saved phase at the next solve and phase saving takes over from there - it is not forced for every
+    /// later decision as Glucose's `setPolarity` is, which is why these are inherent methods and not rustsat's `PhaseLit`
+    /// (INTEGRATION.md).  Kept on the handle until cleared; failed / core stay valid; never makes a warm solve start cold.
+    pub fn phase_hint(&mut self, lit: Lit) -> anyhow::Result<()> {
+        if unsafe { mi355sat_phase(self.h, ipasir(lit)) } < 0 { return Err(self.err()); }
+        Ok(())
+    }
+    /// Drops the hint of `var` (`mi355sat_unphase`).  What the hint seeded stays the workers' saved phase.
+    pub fn clear_phase_hint(&mut self, var: Var) -> anyhow::Result<()> {
+        if unsafe { mi355sat_unphase(self.h, var.idx32() as i32 + 1) } < 0 { return Err(self.err()); }
+        Ok(())
+    }
+    /// Bulk hints (`mi355sat_set_phases`) for the variables 0..=max_var of `assign`: True / False first, DontCare clears
+    /// the variable's hint.  The refinement loop's lever: hint the next bound's fresh solver to the model of the last
+    /// one, restricted to the encoder's variables.
+    pub fn set_phase_hints(&mut self, assign: &Assignment) -> anyhow::Result<()> {
+        let n = assign.max_var().map_or(0, |v| v.idx() + 1);
+        let phases: Vec<i8> = (0..n).map(|i| match assign.var_value(Var::new(i as u32)) {
+            TernaryVal::True => 1, TernaryVal::False => -1, TernaryVal::DontCare => 0 }).collect();
+        if unsafe { mi355sat_set_phases(self.h, phases.as_ptr(), n as u64) } < 0 { return Err(self.err()); }
         Ok(())
     }
     fn err(&self) -> anyhow::Error {

@@ -1,5 +1,5 @@
 // tbs_cli — minimal command-line driver of the solve path (NOT the reference's REPL/UI):
-//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate]
+//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate]
 //   tbs_cli file PATH.toml [-l1:K] ...
 // Mirrors `solve -l<dims>:<n>` of crates/repl/src/main.rs:44-75,248-261: encode once, then solver_loop.
 // Ctrl-C calls mi355sat_interrupt (main.rs:297-324).
@@ -23,7 +23,7 @@ int main(int argc, char** argv) {
     using namespace tbs;
     try {
         if (argc < 3) {
-            fprintf(stderr, "usage: %s rect W H | file PATH [-l<dims>:<n>]... [--platforms default|1x1] [--workers N] [--sweep | --incremental] [--gpu N] [--seed N] "
+            fprintf(stderr, "usage: %s rect W H | file PATH [-l<dims>:<n>]... [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] "
                             "[--verbose] [--no-simp] [--eliminate]\n", argv[0]);
             return 2;
         }
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
         PlatformLimits limits;
         mi355sat_opts opts{};
         opts.device = -1;
-        bool sweep = false, incremental = false;
+        bool sweep = false, incremental = false, phase_hints = false;
         for (; a < argc; a++) {
             std::string arg = argv[a];
             if (arg.rfind("-l", 0) == 0) {             // -l<dims>:<n>, dims = AxB or A (=AxA), main.rs:120-142
@@ -58,6 +58,7 @@ int main(int argc, char** argv) {
             else if (arg == "--eliminate") opts.simp = 2;     // + bounded variable elimination before every search
             else if (arg == "--sweep") sweep = true;   // the bounds below the first one as one batch on the device
             else if (arg == "--incremental") incremental = true;   // one warm handle for the whole ladder (mi355sat_set_incremental)
+            else if (arg == "--phase-hints") phase_hints = true;   // every rung starts its search at the layout of the rung before (mi355sat_set_phases)
             else throw std::runtime_error("unknown argument " + arg);
         }
         Encoding enc = Encoding::encode(defs, grid);
@@ -65,7 +66,7 @@ int main(int argc, char** argv) {
         auto print = [](const std::string& l) { std::cout << l << std::endl; };
         auto hist = incremental ? solver_loop_incremental(grid, enc, limits, &opts, print, [](mi355sat* s) { g_current.store(s); })
                     : sweep ? solver_loop_sweep(grid, enc, limits, &opts, print, [](mi355sat* s) { g_current.store(s); }, &g_interrupted)
-                            : solver_loop(grid, enc, limits, &opts, print, [](mi355sat* s) { g_current.store(s); });
+                            : solver_loop(grid, enc, limits, &opts, print, [](mi355sat* s) { g_current.store(s); }, (size_t)-1, phase_hints);
         return hist.empty() ? 1 : 0;
     } catch (const std::exception& e) {
         fprintf(stderr, "Error: %s\n", e.what());

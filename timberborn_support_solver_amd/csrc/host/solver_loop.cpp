@@ -7,7 +7,8 @@
 namespace tbs {
 
 SolverResult run_solver(const Cnf& cnf, const mi355sat_opts* opts, std::vector<int8_t>& model,
-                        mi355sat_stats_t& stats, const std::function<void(mi355sat*)>& on_interrupter) {
+                        mi355sat_stats_t& stats, const std::function<void(mi355sat*)>& on_interrupter,
+                        const std::vector<int8_t>* phase_hints) {
     mi355sat* s = mi355sat_new(opts);  // GlucoseSimp::default(), main.rs:295
     if (!s) throw std::runtime_error(std::string("Failed to create solver: ") + mi355sat_last_error(nullptr));
     auto fail = [&](const char* ctx) {
@@ -17,6 +18,8 @@ SolverResult run_solver(const Cnf& cnf, const mi355sat_opts* opts, std::vector<i
     };
     if (mi355sat_add_cnf(s, cnf.lits.data(), cnf.offsets.data(), cnf.n_clauses()) < 0) fail("Failed to add CNF");
     mi355sat_reserve(s, cnf.n_vars);
+    if (phase_hints && !phase_hints->empty() &&
+        mi355sat_set_phases(s, phase_hints->data(), std::min<uint64_t>(phase_hints->size(), cnf.n_vars)) < 0) fail("set_phases");
     if (on_interrupter) on_interrupter(s);   // solver.interrupter(), solver_runner.rs:13
     int rc = mi355sat_solve(s);              // solver_runner.rs:16
     if (rc < 0) fail("solve");
@@ -31,9 +34,11 @@ SolverResult run_solver(const Cnf& cnf, const mi355sat_opts* opts, std::vector<i
 std::vector<LoopIteration> solver_loop(const WorldGrid& world, const Encoding& encoding, PlatformLimits limits,
                                        const mi355sat_opts* opts,
                                        const std::function<void(const std::string&)>& out,
-                                       const std::function<void(mi355sat*)>& on_interrupter, size_t max_iterations) {
+                                       const std::function<void(mi355sat*)>& on_interrupter, size_t max_iterations,
+                                       bool phase_hints) {
     std::vector<LoopIteration> hist;
     const Dims one{1, 1};
+    std::vector<int8_t> hints;     // phase_hints: the encoder's variables of the last model (the last layout)
     while (hist.size() < max_iterations) {
         Cnf cnf = encoding.with_limits(limits).into_cnf();   // main.rs:292-293
         LoopIteration it;
@@ -41,7 +46,7 @@ std::vector<LoopIteration> solver_loop(const WorldGrid& world, const Encoding& e
         it.k = lim == limits.card_limits.end() ? (size_t)-1 : lim->second;
         std::vector<int8_t> model;
         auto t0 = std::chrono::steady_clock::now();
-        it.result = run_solver(cnf, opts, model, it.stats, on_interrupter);
+        it.result = run_solver(cnf, opts, model, it.stats, on_interrupter, phase_hints ? &hints : nullptr);
         it.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (it.result == SolverResult::Unsat) {
             out("No solution found for the current constraints");   // main.rs:332
@@ -61,6 +66,8 @@ std::vector<LoopIteration> solver_loop(const WorldGrid& world, const Encoding& e
             return hist;
         }
         limits.card_limits[one] = it.count - 1;                      // main.rs:346
+        // the totalizer's auxiliaries differ from bound to bound: only the encoder's variables carry over
+        if (phase_hints) hints.assign(model.begin(), model.begin() + std::min<size_t>(model.size(), encoding.instance().n_vars));
         out("Solution found (" + std::to_string(it.count) + " platforms total)");
         for (auto& kv : it.layout.platform_stats())
             out(std::to_string(kv.first.w) + "x" + std::to_string(kv.first.h) + ": " + std::to_string(kv.second));

@@ -25,17 +25,21 @@ struct LoopIteration {
 };
 
 // run_solver: fresh solver, add_cnf, hand the interrupter out, solve.  `on_interrupter` receives
-// the handle whose mi355sat_interrupt() may be called from any thread while solve() runs.
+// the handle whose mi355sat_interrupt() may be called from any thread while solve() runs.  `phase_hints` (may be null):
+// phase hints for variables 1..size (mi355sat_set_phases), set before the solve.
 SolverResult run_solver(const Cnf& cnf, const mi355sat_opts* opts, std::vector<int8_t>& model,
-                        mi355sat_stats_t& stats, const std::function<void(mi355sat*)>& on_interrupter = {});
+                        mi355sat_stats_t& stats, const std::function<void(mi355sat*)>& on_interrupter = {},
+                        const std::vector<int8_t>* phase_hints = nullptr);
 
 // solver_loop: repeat { with_limits -> into_cnf -> fresh solver -> solve -> layout -> k := count-1 }
 // until Unsat / Interrupted / a layout without platforms; prints the reference's messages via `out`.
+// phase_hints (opt-in, tbs_cli --phase-hints): after a Sat rung the next rung's fresh solver is hinted to the model just
+// found, on the encoder's variables (the last layout), so that it starts its search there (mi355sat_set_phases).
 std::vector<LoopIteration> solver_loop(const WorldGrid& world, const Encoding& encoding, PlatformLimits limits,
                                        const mi355sat_opts* opts,
                                        const std::function<void(const std::string&)>& out,
                                        const std::function<void(mi355sat*)>& on_interrupter = {},
-                                       size_t max_iterations = (size_t)-1);
+                                       size_t max_iterations = (size_t)-1, bool phase_hints = false);
 
 // The same refinement as ONE batch on the device: every bound k0, k0-1, ..., 0 is an assumption
 // set over one CNF built for k0; a SAT model with c platforms answers every bound >= c, an UNSAT bound every

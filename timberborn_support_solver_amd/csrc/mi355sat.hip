@@ -114,6 +114,24 @@ __global__ void ms_replicate_kernel(const char* tmpl, char* slabs, uint64_t slab
     }
 }
 
+// Phase hints (mi355sat_phase / mi355sat_set_phases): seeds the saved phase of every hinted, still unassigned variable of
+// workers [wid0, n_workers).  hints[v]: 0 none, 1 TRUE first, 2 FALSE first, one byte per device variable.  One variable
+// per thread, grid = (ceil(n_vars / 256), workers): a coalesced read of the hint bytes; only a hinted variable touches the
+// worker's slab (its assignment byte, then one byte store).  An assigned variable's phase byte is its polarity now
+// (layout.h, MsVarRec) and is left alone.  Runs between slices only, when the slab is the whole truth in every build of
+// the search kernel.
+__global__ __launch_bounds__(256) void ms_phase_kernel(MsLayout L, char* slabs, uint32_t wid0, uint32_t n_workers,
+                                                       const uint8_t* hints) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t wid = wid0 + blockIdx.y;
+    if (v >= L.n_vars || wid >= n_workers) return;
+    const uint8_t h = ((Gp<const uint8_t>)hints)[v];
+    if (!h) return;
+    Gp<char> slab = (Gp<char>)(slabs + (size_t)wid * L.slab_bytes);
+    if (((Gp<const uint8_t>)(slab + L.val))[v] != MS_ASG_UNDEF) return;
+    ((Gp<MsVarRec>)(slab + L.vrec))[v].phase = (uint8_t)(h - 1);   // device literal 2*v + phase: phase 1 = the negative one
+}
+
 // Applies the scheduler's decisions between two slices: update u = (worker, status, restart_req,
 // n_assumps, data offset); the worker's assumption list (its cube) is rewritten from data[].
 __global__ void ms_assign_kernel(MsLayout L, char* slabs, uint32_t n_upd, const int32_t* upd, const int32_t* data) {
@@ -401,6 +419,17 @@ struct mi355sat {
     } inc;
     DevBuf<int32_t> d_inc_lits;
     DevBuf<uint32_t> d_inc_offs;
+    // phase hints (mi355sat_phase / mi355sat_set_phases): kept on the handle in the caller's variables; every cold start maps
+    // them to the device's (map_phases) and seeds every worker's saved phases with them (ms_phase_kernel)
+    struct Phases {
+        std::vector<int8_t> hint;              // per caller variable (index v - 1): 0 none, 1 TRUE first, -1 FALSE first
+        uint64_t version = 0;                  // bumped whenever a hint changes ...
+        uint64_t applied = 0;                  // ... and the one the workers on the device were last seeded with
+        std::vector<uint8_t> dev_fixed;        // per device variable: assigned at level 0 by the last cold start's upload
+        bool on_device = false;                // d_phase holds the current hints in the current mapping (mapped > 0 of them)
+        mi355sat_phase_info info{};
+    } ph;
+    DevBuf<uint8_t> d_phase;
     // test hooks: the optional heuristics' counters over the workers of the last solve; their schedule (0 = the defaults)
     mi355sat_heuristics_info heur{};
     uint32_t first_vivify = 0, vivify_every = 0, rephase_every = 0;
@@ -898,6 +927,57 @@ void customize(mi355sat& s, const std::vector<int32_t>* assump, const std::vecto
     HIPCHK(hipGetLastError());
 }
 
+// ---- phase hints -------------------------------------------------------------------------------------------------------
+// The handle's hints in the device's variables, as ms_phase_kernel reads them (one byte per device variable: 0 none, 1
+// TRUE first, 2 FALSE first), uploaded: through the equivalent-literal substitution, which may flip the sign, then the
+// device's variable order - the route of the assumptions (map_assumptions).  In increasing caller-variable order, so of
+// two hints that meet on one representative the later one wins.  An eliminated variable has no device variable, one
+// fixed at level 0 no phase to seed: counted.
+void map_phases(mi355sat& s) {
+    mi355sat::Phases& ph = s.ph;
+    std::vector<uint8_t> bytes(s.n_vars, 0), gone(s.n_vars, 0);
+    for (const MsElim& e : s.elims) gone[e.x >> 1] = 1;
+    ph.info.dropped_eliminated = ph.info.dropped_fixed = ph.info.mapped = 0;
+    for (size_t v = 0; v < ph.hint.size() && v < s.n_vars; v++) {
+        if (!ph.hint[v]) continue;
+        int32_t l = 2 * (int32_t)v + (ph.hint[v] < 0 ? 1 : 0);
+        while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
+        if (gone[l >> 1]) { ph.info.dropped_eliminated++; continue; }
+        const uint32_t dv = s.perm[l >> 1];
+        if (dv < ph.dev_fixed.size() && ph.dev_fixed[dv]) { ph.info.dropped_fixed++; continue; }
+        bytes[dv] = (uint8_t)(1 + (l & 1));
+    }
+    for (uint8_t b : bytes) ph.info.mapped += b != 0;
+    ph.on_device = ph.info.mapped > 0;
+    if (ph.on_device) s.d_phase.upload(bytes, s.stream);
+}
+
+// Seeds workers [from, to) with the hints on the device (nothing to do without any), on the stream.
+void seed_phases(mi355sat& s, uint32_t from, uint32_t to) {
+    if (!s.ph.on_device || to <= from || s.L.n_vars == 0) return;
+    for (uint32_t w = from; w < to; w += 32768) {   // (gridDim.y is a 16-bit number)
+        const uint32_t n = std::min(to - w, 32768u);
+        hipLaunchKernelGGL(ms_phase_kernel, dim3((s.L.n_vars + 255) / 256, n), dim3(256), 0, s.stream, s.L, s.d_slabs.p, w, w + n,
+                           (const uint8_t*)s.d_phase.p);
+        HIPCHK(hipGetLastError());
+        s.ph.info.launches++;
+    }
+}
+
+// A cold start seeds every worker it created; a warm one the resident workers, and only if a hint changed since they
+// were last seeded (they keep the phases they saved otherwise).  The workers stand at level 0 in both cases.
+void apply_phases(mi355sat& s, bool warm) {
+    mi355sat::Phases& ph = s.ph;
+    if (warm && ph.applied == ph.version) return;
+    ph.applied = ph.version;
+    ph.on_device = false;
+    if (!ph.info.hinted) return;     // (a cleared hint takes nothing back: what it seeded is the worker's saved phase now)
+    map_phases(s);
+    seed_phases(s, 0, s.n_alloc);
+    HIPCHK(hipStreamSynchronize(s.stream));
+    (warm ? ph.info.applied_warm : ph.info.applied_cold)++;
+}
+
 // The search outlived the ramp-up's first phase: give the remaining workers their slabs.  The running workers'
 // slabs move into the full-size buffer (device-to-device copy), the new ones start from the template with the
 // assumption list of instance w % n_instances, as at the beginning.
@@ -924,6 +1004,7 @@ void grow_workers(mi355sat& s, uint32_t n_instances, uint32_t target) {
                        s.d_assump.p, s.d_assump_off.p, (const int32_t*)nullptr, (const uint64_t*)nullptr, n_instances, s.opts.seed,
                        -1, old, s.opts.phase_mix);
     HIPCHK(hipGetLastError());
+    seed_phases(s, old, s.n_alloc);      // the phase hints, as the workers of the first stage got them
     HIPCHK(hipStreamSynchronize(s.stream));
     if (s.opts.verbose) fprintf(stderr, "[mi355sat] grew from %u to %u worker slabs (%.1f GiB): %.3f s\n", old, s.n_alloc,
                                 (double)s.n_alloc * s.L.slab_bytes / 1073741824.0, now_s() - t0);
@@ -1733,6 +1814,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     sw.ramp_ms = 0;
     sw.core_flag.assign(sw.cores ? n_instances : 0, {});
     for (size_t i = 0; i < sw.core_flag.size(); i++) sw.core_flag[i].assign(assump_off[i + 1] - assump_off[i], 0);
+    s.ph.on_device = false;              // (the mapping of the hints on the device was the last upload's)
     if (P.unsat) {
         std::fill(sw.results.begin(), sw.results.end(), MI355SAT_UNSAT);
         sw.decided = n_instances;
@@ -1772,6 +1854,9 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     }
     reset_workers(s);
     customize(s, &a_int, &a_off, nullptr, nullptr, n_instances, sw.split ? (int32_t)n_instances : -1);
+    s.ph.dev_fixed.assign(P.n_vars, 0);
+    for (int32_t l : P.units) s.ph.dev_fixed[l >> 1] = 1;
+    apply_phases(s, /*warm=*/false);     // after the customisation: a hint outranks opts.phase_mix
     HIPCHK(hipStreamSynchronize(s.stream));
     const uint32_t W = s.n_workers;
     s.stats.workers = W;
@@ -2107,6 +2192,7 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
         }
     }
     sw.sts = sts;
+    if (sw.decided == 0) apply_phases(s, /*warm=*/true);    // every worker stands at level 0 (attach_clauses)
     return MI355SAT_COLD_NONE;
 }
 
@@ -2381,7 +2467,7 @@ void mi355sat_free(mi355sat* s) {
     s->d_template.release(); s->d_slabs.release(); s->d_states.release(); s->d_any_done.release();
     s->d_proof.release(); s->d_proof_len.release();
     s->d_assump.release(); s->d_script.release(); s->d_assump_off.release(); s->d_script_off.release();
-    s->d_inc_lits.release(); s->d_inc_offs.release();
+    s->d_inc_lits.release(); s->d_inc_offs.release(); s->d_phase.release();
     if (s->stop_flag) (void)hipHostFree(s->stop_flag);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -2480,6 +2566,58 @@ int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap,
         return instance >= s->batch_core_valid.size() && !s->batch_core_valid.empty() ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
     }
     return copy_core(s, s->batch_cores[instance], out, cap, n);
+}
+
+// ---- phase hints: kept in the caller's variables; the next cold start (or a warm one, if they changed) applies them
+static int set_hint(mi355sat* s, uint64_t v, int8_t h) {      // v 1-based
+    mi355sat::Phases& ph = s->ph;
+    if (v > ph.hint.size()) {
+        if (!h) return 0;
+        ph.hint.resize(v, 0);
+    }
+    int8_t& cur = ph.hint[v - 1];
+    if (cur == h) return 0;
+    ph.info.hinted += (h != 0) - (cur != 0);
+    cur = h;
+    ph.version++;
+    return 0;
+}
+
+int mi355sat_phase(mi355sat* s, int32_t lit) {
+    if (!s) return MI355SAT_ERR_ARG;
+    const uint64_t v = (uint64_t)(lit < 0 ? -(int64_t)lit : lit);
+    if (lit == 0 || v > MS_MAX_VARS) { s->err = "phase literal out of range"; return MI355SAT_ERR_ARG; }
+    try {
+        set_hint(s, v, lit > 0 ? 1 : -1);
+    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    if (v > s->max_var) { s->max_var = v; s->stats.max_var = v; }   // as mi355sat_reserve
+    return 0;
+}
+
+int mi355sat_unphase(mi355sat* s, int32_t var) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (var <= 0 || (uint64_t)var > MS_MAX_VARS) { s->err = "variable out of range"; return MI355SAT_ERR_ARG; }
+    return set_hint(s, (uint64_t)var, 0);
+}
+
+int mi355sat_set_phases(mi355sat* s, const int8_t* phases, uint64_t n_vars) {
+    if (!s || (n_vars && !phases)) return MI355SAT_ERR_ARG;
+    if (n_vars > MS_MAX_VARS) { s->err = "variable index too large"; return MI355SAT_ERR_ARG; }
+    try {
+        uint64_t top = 0;
+        for (uint64_t v = 1; v <= n_vars; v++) {
+            set_hint(s, v, phases[v - 1] > 0 ? 1 : (phases[v - 1] < 0 ? -1 : 0));
+            if (phases[v - 1]) top = v;
+        }
+        if (top > s->max_var) { s->max_var = top; s->stats.max_var = top; }
+    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    return 0;
+}
+
+int mi355sat_debug_phases(const mi355sat* s, mi355sat_phase_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    *out = s->ph.info;
+    return 0;
 }
 
 int mi355sat_set_proof_path(mi355sat* s, const char* path) {
@@ -2603,6 +2741,7 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
         HIPCHK(hipSetDevice(s->device));
         s->inc.resident = false;     // (the slabs become this batch's)
         s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
+        s->ph.on_device = false;     // scripted BCP decides nothing: no phase hints
         Prepared P;
         prepare(*s, /*simplify=*/false, P);
         if (P.unsat) {  // contradictory unit clauses: every instance conflicts before any decision

@@ -21,16 +21,23 @@ def run_solver(solver, cnf):
     return (lambda: (solver.solve(), solver)), interrupter
 
 
-def solver_loop(grid, encoding, limits, make_solver=None, out=print, on_interrupter=None, max_iterations=None):
+def solver_loop(grid, encoding, limits, make_solver=None, out=print, on_interrupter=None, max_iterations=None,
+                phase_hints=False):
     """Returns a list of per-iteration records:
     {k, result, count, valid, seconds, stats}.  `make_solver` builds the backend
-    (default Mi355Sat()), mirroring `GlucoseSimp::default()` at main.rs:295."""
+    (default Mi355Sat()), mirroring `GlucoseSimp::default()` at main.rs:295.
+    phase_hints (opt-in): after a Sat rung the next rung's fresh solver is hinted to the model just found, on the
+    encoder's variables only (the totalizer's auxiliaries differ from bound to bound): its search starts at the last
+    layout (Mi355Sat.set_phases)."""
     make_solver = make_solver or (lambda: Mi355Sat())
     limits = PlatformLimits(dict(limits.card_limits))
     history = []
+    hints = None
     while max_iterations is None or len(history) < max_iterations:
         cnf = encoding.with_limits_into_cnf(limits)
         solver = make_solver()
+        if hints is not None:
+            solver.set_phases(hints)
         thunk, interrupter = run_solver(solver, cnf)
         if on_interrupter:
             on_interrupter(interrupter)
@@ -48,8 +55,11 @@ def solver_loop(grid, encoding, limits, make_solver=None, out=print, on_interrup
             out("Solver interrupted")
             solver.close()
             return history
-        layout = PlatformLayout.from_assignment(solver.full_solution(encoding.n_vars), encoding)
+        model = solver.full_solution(encoding.n_vars)
+        layout = PlatformLayout.from_assignment(model, encoding)
         solver.close()
+        if phase_hints:
+            hints = model
         count = layout.platform_count()
         rec["count"] = count
         rec["layout"] = layout

@@ -86,6 +86,14 @@ class Mi355SatHeuristicsInfo(ctypes.Structure):   # mi355sat_heuristics_info (te
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatPhaseInfo(ctypes.Structure):   # mi355sat_phase_info (test hook)
+    _fields_ = [(n, ctypes.c_uint64) for n in ("hinted", "applied_cold", "applied_warm", "launches", "mapped",
+                                               "dropped_eliminated", "dropped_fixed")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
     NONE = 0
     FIRST = 1
@@ -153,6 +161,10 @@ def _bind(L):
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
     L.mi355sat_debug_set_schedule.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+    L.mi355sat_phase.argtypes = [vp, ctypes.c_int32]
+    L.mi355sat_unphase.argtypes = [vp, ctypes.c_int32]
+    L.mi355sat_set_phases.argtypes = [vp, vp, ctypes.c_uint64]
+    L.mi355sat_debug_phases.argtypes = [vp, ctypes.POINTER(Mi355SatPhaseInfo)]
     L.mi355sat_share_export.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_share_import.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     return L
@@ -269,6 +281,33 @@ class Mi355Sat:
     def core_of(self, instance):
         """The same for an Unsat instance of the last solve_batch()."""
         return self._core(self._L.mi355sat_core_of, instance)
+
+    # ---- phase hints (rustsat PhaseLit's place; seeded, not forced: include/mi355sat.h)
+    def phase(self, lit):
+        """Hint: the first time var(lit) is decided, it is decided as lit.  Seeds the workers' saved phase at the next
+        solve; phase saving takes over from there.  Kept until unphase()."""
+        self._check(self._L.mi355sat_phase(self._h, int(lit)), "phase")
+        self._n_vars = max(self._n_vars, abs(int(lit)))
+
+    def unphase(self, var):
+        """Drop the hint of variable `var`."""
+        self._check(self._L.mi355sat_unphase(self._h, int(var)), "unphase")
+
+    def set_phases(self, phases):
+        """Bulk hints for variables 1..len(phases): > 0 TRUE first, < 0 FALSE first, 0 none (clears one) - a model as
+        full_solution() returns it is a valid argument."""
+        ph = np.ascontiguousarray(np.sign(np.asarray(phases)), dtype=np.int8)
+        self._check(self._L.mi355sat_set_phases(self._h, _p(ph), len(ph)), "set_phases")
+        nz = np.flatnonzero(ph)
+        if nz.size:
+            self._n_vars = max(self._n_vars, int(nz[-1]) + 1)
+
+    def debug_phases(self):
+        """Test hook: hinted variables now; cold / warm starts that seeded their workers; ms_phase_kernel launches; at the
+        last application the device variables seeded per worker and the hints dropped (eliminated / fixed variables)."""
+        info = Mi355SatPhaseInfo()
+        self._check(self._L.mi355sat_debug_phases(self._h, ctypes.byref(info)), "debug_phases")
+        return info.as_dict()
 
     def solve_batch(self, assumption_sets, stop_at_first=False):
         """assumption_sets: list of lists of DIMACS literals.  Returns [SolverResult]."""
