@@ -201,11 +201,65 @@ int mi355sat_assume(mi355sat* s, int32_t lit);
  * other state (no solve yet, SAT, interrupted, exhausted budget, a clause or an assumption added since). */
 int mi355sat_failed(mi355sat* s, int32_t lit);
 /* The core of the last UNSAT solve(): a subset of the assumptions as the caller gave them, in their order, such that
- * formula AND core is UNSAT (empty if the formula alone is).  Not minimised.  out may be NULL to size the buffer;
+ * formula AND core is UNSAT (empty if the formula alone is).  As the final conflict left it: mi355sat_minimize_core()
+ * shrinks it to an irreducible one.  out may be NULL to size the buffer;
  * *n receives the length; MI355SAT_ERR_ARG if cap is too small, MI355SAT_ERR_STATE as for mi355sat_failed(). */
 int mi355sat_core(mi355sat* s, int32_t* out, uint64_t cap, uint64_t* n);
 /* The same for instance i of the last mi355sat_solve_batch() that reported UNSAT (MI355SAT_ERR_STATE otherwise). */
 int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n);
+
+/* --- irreducible cores ------------------------------------------------------- */
+/* Shrinks the core of the last UNSAT solve() (mi355sat_minimize_core_of: of instance i of the last solve_batch()) until no
+ * literal can be left out: afterwards mi355sat_core / _failed / _core_of answer with the new core - a subset of the old
+ * one, in the caller's order, without repeats, formula AND core still UNSAT - until the next solve or add, as before.
+ * Valid exactly where mi355sat_core / _core_of is, MI355SAT_ERR_STATE otherwise (and during a mi355sat_sweep_*); as
+ * mi355sat_core_of, _minimize_core_of answers an instance index beyond the last batch with MI355SAT_ERR_ARG, and a
+ * negative conflict_budget is MI355SAT_ERR_ARG too.
+ * Returns 0 or a negative error; after an error the core is the one from before the call.
+ *   - Deletion by rounds, on the device: a round poses up to min(64, workers) candidates "the core without this chunk"
+ *     side by side as the instances of ONE resident sweep - the formula is simplified and uploaded once per call, the
+ *     workers move from candidate to candidate and keep their learnt clauses, phases and the exchange ring (all
+ *     consequences of the formula alone).  An UNSAT candidate's own final-conflict core becomes the working core; a SAT
+ *     candidate that left out one literal proves it necessary, one that left out more proves a literal necessary if it is
+ *     the only one its model falsifies (critical_by_model).  Rounds of SAT answers that prove nothing halve the chunks.
+ *   - minimal = 1: formula AND (core without c) is SAT for every c in the core.  minimal = 0: the call stopped early -
+ *     conflict_budget (> 0: conflicts summed over workers; opts.conflict_budget does not apply) or mi355sat_interrupt(),
+ *     which the call consumes; an interrupt that came before the call leaves the core unchanged.  The core is then a
+ *     valid core no larger than before.
+ *   - Nothing is launched or allocated for an empty core, for a core this call (or an earlier one) already proved
+ *     irreducible (the flag is kept with the core: candidates = 0), and for a one-literal core when the handle has
+ *     answered SAT since the last clause was added (the formula alone has a model: the loop's bound posed as an
+ *     assumption after a satisfiable one).  Any other one-literal core costs one candidate, the empty set.
+ *   - opts and stats keep their layout.  Candidates do not count in n_sat / n_unsat / n_terminated; solve_seconds,
+ *     kernel_seconds, kernel_launches and the event counters accumulate; simp_* and workers keep describing the caller's
+ *     last solve / batch, while learnts / learnt_literals and the test hooks that describe "the last search"
+ *     (mi355sat_debug_last_search_build, _debug_heuristics, _debug_share_ring, an armed _debug_keep_simplified) then
+ *     describe the call's own sweep, which is what is on the device.  No proof lines are written.  opts.cube_split does
+ *     not apply.
+ *     For the warm incremental mode the call is another search in between: the next solve() starts cold
+ *     (MI355SAT_COLD_OTHER_SEARCH).
+ * Measured on the MI355X (profiles/r07_core_minimize.log: "no platform at any anchor", 1x1 platforms, rect 16 / 24 / 32 with
+ * 256 / 576 / 1024 assumptions, three runs each way, alternating): the final conflict's core has 10 literals and is
+ * irreducible already, so the call is one round of ten candidates - 11 / 23 / 23-24 ms beside a solve() of 3-9 ms - and the
+ * same deletion loop driven from outside with one cold mi355sat_solve_batch per round takes the same 11 / 23 / 23-24 ms:
+ * with one round the resident sweep gains nothing.  Cores that shrink over several rounds have not been measured on the
+ * device. */
+typedef struct mi355sat_core_min_info {
+    uint64_t size_before, size_after;
+    int32_t  minimal;            /* 1: every literal of the core is proved necessary; 0: stopped early (budget / interrupt) */
+    uint32_t rounds;
+    uint64_t candidates;         /* assumption sets posed */
+    uint64_t candidates_unsat, candidates_sat;
+    uint64_t critical_by_model;  /* literals proved necessary by a SAT candidate that dropped MORE than that one literal */
+    uint64_t model_launches;     /* launches of ms_core_model_kernel */
+    uint64_t conflicts;
+    double   seconds;
+} mi355sat_core_min_info;
+int mi355sat_minimize_core(mi355sat* s, int64_t conflict_budget, mi355sat_core_min_info* out /* may be NULL */);
+int mi355sat_minimize_core_of(mi355sat* s, uint64_t instance, int64_t conflict_budget, mi355sat_core_min_info* out);
+/* Test hook: at most max_candidates candidates per round (0 = the default, min(64, workers)): forces rounds of chunks of
+ * several literals on cores that one round would hold. */
+int mi355sat_debug_core_min_round(mi355sat* s, uint32_t max_candidates);
 
 /* --- phase hints (rustsat PhaseLit's place; seeded, not forced) ------------- */
 /* A hint tells the search which polarity to try FIRST for a variable: the first time var(lit) is decided, it is decided

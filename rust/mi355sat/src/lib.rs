@@ -37,6 +37,17 @@ pub struct Stats {
     pub shared_imported_units: u64, pub simp_units: u64, pub simp_equivalences: u64, pub simp_clauses_removed: u64, pub workers: u64, pub simp_eliminated: u64,
 }
 
+/// Mirror of `mi355sat_core_min_info`: what `minimize_core` did.
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct CoreMinInfo {
+    pub size_before: u64, pub size_after: u64,
+    /// 1: every literal of the core is proved necessary; 0: stopped early (budget / interrupt), the core is still a core
+    pub minimal: i32,
+    pub rounds: u32, pub candidates: u64, pub candidates_unsat: u64, pub candidates_sat: u64,
+    pub critical_by_model: u64, pub model_launches: u64, pub conflicts: u64, pub seconds: f64,
+}
+
 extern "C" {
     fn mi355sat_new(opts: *const Opts) -> *mut c_void;
     fn mi355sat_free(s: *mut c_void);
@@ -49,6 +60,7 @@ extern "C" {
     fn mi355sat_val(s: *mut c_void, lit: i32) -> i32;
     fn mi355sat_assume(s: *mut c_void, lit: i32) -> c_int;
     fn mi355sat_core(s: *mut c_void, out: *mut i32, cap: u64, n: *mut u64) -> c_int;
+    fn mi355sat_minimize_core(s: *mut c_void, conflict_budget: i64, out: *mut CoreMinInfo) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
     fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
@@ -106,6 +118,17 @@ impl Mi355Sat {
             TernaryVal::True => 1, TernaryVal::False => -1, TernaryVal::DontCare => 0 }).collect();
         if unsafe { mi355sat_set_phases(self.h, phases.as_ptr(), n as u64) } < 0 { return Err(self.err()); }
         Ok(())
+    }
+    /// Irreducible core (`mi355sat_minimize_core`): after `solve_assumps` returned `Unsat`, shrinks the core until no
+    /// literal can be left out; `core()` answers with the new one, a subsequence of the old.  `budget`: conflicts summed
+    /// over the workers (None: no limit); with `minimal == 0` the budget or an interrupt ended the call early and the
+    /// core is still a valid core.  An error (`MI355SAT_ERR_STATE`) where `core()` would give one.  What core-guided code
+    /// wants before it adds a totalizer per core literal.  Replayed in C by tests/abi_core_minimize.c.
+    pub fn minimize_core(&mut self, budget: Option<u64>) -> anyhow::Result<CoreMinInfo> {
+        let mut info = CoreMinInfo::default();
+        let b = budget.map_or(0, |b| b.clamp(1, i64::MAX as u64) as i64);
+        if unsafe { mi355sat_minimize_core(self.h, b, &mut info) } < 0 { return Err(self.err()); }
+        Ok(info)
     }
     fn err(&self) -> anyhow::Error {
         let m = unsafe { std::ffi::CStr::from_ptr(mi355sat_last_error(self.h)) };

@@ -2748,6 +2748,56 @@ __global__ __launch_bounds__(MS_WAVE) void ms_final_kernel(MsShared sh, MsLayout
     if (lane == 0) ok[b] = bad ? 0 : 1;
 }
 
+// ---- a model at a few positions (core minimisation, mi355sat_minimize_core) ---------------
+// Which literals of a short list a model falsifies.  One workgroup (one wave) per worker that came back MS_ST_SAT; the
+// worker's slab is only READ.  Block b looks at the device literals q_lits[q_off[b] .. q_off[b + 1]) - the literals of
+// the working core its worker did NOT assume - 64 per round, one per lane: the variable's assignment byte in the slab,
+// which between two slices is the whole truth in every build of the search kernel (wk_store writes a staged assignment
+// back), so this kernel has one build.  The ballot of a round is two words of the block's row of `out` (bit i = entry
+// i of the block's list is FALSE: ms_final_kernel's layout); every word of the row is written, no lane writes a word
+// another lane writes.  The worker's own assumption list is read the same way: in a model every one of them is TRUE.
+// ok[b] = 0 if the slab is no model (status, an assumption that is not true, an unassigned or out-of-range literal, a
+// list longer than the row), which the host reports as an internal error.  No LDS, no atomics, nothing written to a slab.
+__global__ __launch_bounds__(MS_WAVE) void ms_core_model_kernel(MsLayout L, const char* slabs, const int32_t* workers,
+                                                               const int32_t* q_lits, const uint32_t* q_off, uint32_t* out,
+                                                               uint32_t out_words, int32_t* ok) {
+    const int lane = (int)threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const int wid = uni(((Gp<const int32_t>)workers)[b]);
+    Gp<const char> slab = (Gp<const char>)(slabs + (size_t)wid * L.slab_bytes);
+    Gp<const MsState> st = (Gp<const MsState>)(slab + L.state);
+    Gp<const int32_t> assumps = (Gp<const int32_t>)(slab + L.assumps);
+    Gp<const uint8_t> val = (Gp<const uint8_t>)(slab + L.val);
+    Gp<const int32_t> ql = (Gp<const int32_t>)q_lits;
+    Gp<uint32_t> row = (Gp<uint32_t>)out + (size_t)b * out_words;
+    const int n_a = uni(st->n_assumps);
+    const uint32_t q0 = (uint32_t)uni((int)((Gp<const uint32_t>)q_off)[b]), q1 = (uint32_t)uni((int)((Gp<const uint32_t>)q_off)[b + 1]);
+    const uint32_t cap = out_words * 32u, n_q = q1 - q0;
+    bool bad = uni(st->status) != MS_ST_SAT || n_a < 0 || (uint32_t)n_a > L.assump_cap || q1 < q0 || n_q > cap;
+    // the worker's own assumptions: all TRUE in its model
+    for (int i0 = 0; !bad && i0 < n_a; i0 += MS_WAVE) {
+        const int i = i0 + lane;
+        const bool in = i < n_a;
+        const int lit = in ? assumps[i] : 0;
+        const bool inr = (uint32_t)lit < 2u * L.n_vars;
+        const uint32_t x = in && inr ? (uint32_t)val[lit >> 1] : 0u;
+        if (ballot(in && (!inr || x != (uint32_t)(MS_ASG_TRUE | (lit & 1)))) != 0) bad = true;
+    }
+    // the literals it did not assume: bit i = entry i is FALSE
+    for (uint32_t i0 = 0; i0 < cap; i0 += MS_WAVE) {
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool in = !bad && i < n_q;
+        const int lit = in ? ql[q0 + i] : 0;
+        const bool inr = (uint32_t)lit < 2u * L.n_vars;
+        const uint32_t x = in && inr ? (uint32_t)val[lit >> 1] : 0u;
+        if (ballot(in && (!inr || !(x & 2u))) != 0) bad = true;
+        const u64 fm = ballot(in && inr && x == (uint32_t)(MS_ASG_FALSE ^ (lit & 1)));
+        const uint32_t wi = (i0 >> 5) + (uint32_t)lane;      // lanes 0 and 1: the round's two words
+        if (lane < 2 && wi < out_words) row[wi] = bad ? 0u : (uint32_t)(fm >> (32 * lane));
+    }
+    if (lane == 0) ((Gp<int32_t>)ok)[b] = bad ? 0 : 1;
+}
+
 // ---- warm attach (incremental solve) ---------------------------------------------------
 // Clauses the caller added between two solves of one handle go to the workers that are still resident from the solve
 // before (mi355sat_set_incremental): one workgroup (one wave) per worker, between two slices.  Clause c is

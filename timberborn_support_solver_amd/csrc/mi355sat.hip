@@ -402,6 +402,13 @@ struct mi355sat {
     bool core_valid = false;
     std::vector<std::vector<int32_t>> batch_cores;   // of the last solve_batch(), per instance
     std::vector<uint8_t> batch_core_valid;
+    // core minimisation (mi355sat_minimize_core): a core it proved irreducible is not minimised again (the flags fall with
+    // the cores); the formula is known to be satisfiable while no clause was added since a SAT answer; test hook
+    // (mi355sat_debug_core_min_round): at most this many candidates per round, 0 = the default
+    bool core_minimal = false;
+    std::vector<uint8_t> batch_core_minimal;
+    uint64_t sat_clauses = UINT64_MAX;         // stats.n_clauses when a solve / batch last answered SAT
+    uint32_t core_min_round = 0;
     // warm incremental solve (mi355sat_set_incremental): what the last mi355sat_solve() left on the device, and what was
     // attached to it since
     struct Incremental {
@@ -1745,6 +1752,8 @@ struct Sweep {
     std::vector<std::vector<uint8_t>> core_flag;
     DevBuf<int32_t> d_fw, d_fok;
     DevBuf<uint32_t> d_fout, d_fscratch;
+    DevBuf<int32_t> d_qlits;                     // core minimisation: what ms_core_model_kernel looks up (core_models)
+    DevBuf<uint32_t> d_qoff;
     // warm incremental solve: a plain solve() that may leave its workers to the next one (a cold start) or took them over
     // from the one before (a warm start: their counters run on from counters0, conflicts0 = those conflicts summed)
     bool keep_warm = false;
@@ -1778,8 +1787,15 @@ void map_assumptions(const mi355sat& s, const std::vector<uint32_t>& perm, uint3
     }
 }
 
+inline uint32_t fleet_size(const mi355sat& s) {      // opts.workers, or the default by formula size (sweep_begin)
+    return s.opts.workers > 0 ? (uint32_t)s.opts.workers
+                              : (s.offs.size() > 100000 ? MS_SEARCH_WAVES_PER_SIMD * 1024u : (s.offs.size() > 20000 ? 1024u : 256u));
+}
+
+// keep (may be null): caller's literals whose variables must survive the simplification besides the assumptions' - lists
+// that sweep_repose will pose later; their number is also the room the slabs leave for an assumption list.
 int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
-                uint32_t n_instances, bool stop_at_first) {
+                uint32_t n_instances, bool stop_at_first, const std::vector<int32_t>* keep = nullptr) {
     Prepared P;
     {
         Formula F;
@@ -1787,6 +1803,9 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         F.log_proof = !s.proof_path.empty();
         for (int32_t d : assump)
             if (d != 0 && (uint64_t)(d < 0 ? -(int64_t)d : d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
+        if (keep)
+            for (int32_t d : *keep)
+                if (d != 0 && (uint64_t)(d < 0 ? -(int64_t)d : d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
         simplify_formula(s, F);
         if (s.keep_simplified) keep_simplified_copy(s, F);
         build_csr(s, F, /*units_propagated=*/true, P);
@@ -1823,8 +1842,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     }
     // default fleet: the whole GPU (16 waves per CU) for large formulas; mid-size ones measured fastest to a verdict
     // with 1024 workers (rect 24x24 ladder), small ones do not pay for more than one worker per CU
-    uint32_t want = s.opts.workers > 0 ? (uint32_t)s.opts.workers
-                                       : (s.offs.size() > 100000 ? MS_SEARCH_WAVES_PER_SIMD * 1024u : (s.offs.size() > 20000 ? 1024u : 256u));
+    uint32_t want = fleet_size(s);
     if (want < n_instances) want = n_instances;
     want = want / n_instances * n_instances;
     s.d_proof.release();
@@ -1838,6 +1856,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     for (uint32_t i = 0; i < n_instances; i++)
         max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)(a_off[i + 1] - a_off[i]));
     // (a solve that may be followed by warm ones leaves room for their assumption lists)
+    if (keep) max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)keep->size());
     const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps + (sw.keep_warm ? 256u : 0u);
     const uint32_t initial = (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) ? std::max(256u, n_instances) / n_instances * n_instances : 0;
     upload_formula(s, P, assump_cap, 0, want, initial);
@@ -1945,14 +1964,15 @@ inline bool inst_open(const Sweep& sw, uint32_t inst) { return sw.results[inst] 
 // Portfolio mode, between two slices: the workers of instances that are decided (or withdrawn) move to
 // the open instances with the fewest workers.  They keep their learnt clauses (consequences of the
 // formula alone) and only swap their assumption list; the worker holding a SAT instance's model stays.
-void rebalance_workers(mi355sat& s, Sweep& sw) {
+// all (sweep_repose): every instance was posed anew, so every worker that has a slab moves, whatever it worked on.
+void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
     const uint32_t n_instances = sw.n_instances;
     std::vector<uint32_t> cnt(n_instances, 0), movable;
     for (uint32_t w = 0; w < s.n_alloc; w++) {   // (a worker without a slab yet is picked up after grow_workers)
         const uint32_t inst = (uint32_t)sw.w_inst[w];
         const int st = sw.sts[w].status;
-        if (inst_open(sw, inst)) { if (st == MS_ST_RUNNING) cnt[inst]++; continue; }
-        if (sw.winner[inst] == (int32_t)w && sw.results[inst] == MI355SAT_SAT) continue;   // keeps the model
+        if (!all && inst_open(sw, inst)) { if (st == MS_ST_RUNNING) cnt[inst]++; continue; }
+        if (!all && sw.winner[inst] == (int32_t)w && sw.results[inst] == MI355SAT_SAT) continue;   // keeps the model
         if (st == MS_ST_RUNNING || st == MS_ST_SAT || st == MS_ST_REFUTED || st == MS_ST_PARKED) movable.push_back(w);
     }
     std::vector<uint32_t> open;
@@ -1964,7 +1984,7 @@ void rebalance_workers(mi355sat& s, Sweep& sw) {
         sw.sts[w].status = MS_ST_PARKED;
         sw.w_busy[w] = 0;
     };
-    if (open.empty() || s.opts.rebalance < 0) {
+    if (open.empty() || (s.opts.rebalance < 0 && !all)) {
         for (uint32_t w : movable) park(w);
     } else {
         // Each open instance's share of the fleet follows its weight (mi355sat_sweep_set_weights; default equal).
@@ -2392,6 +2412,262 @@ int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vecto
     return rc;
 }
 
+
+// ---- core minimisation (mi355sat_minimize_core) ------------------------------------------------------------------------
+// Deletion-based minimisation of a failed-assumption core as ONE sweep: the formula is simplified, uploaded and replicated
+// once, every round poses its candidates - the working core without one chunk each - into the running sweep
+// (sweep_repose), and the workers keep their learnt clauses, saved phases, decision order and the exchange ring from
+// round to round: all of that follows from the formula alone and holds under every candidate.  DESIGN.md §5.
+
+// Pose `lits` (caller's literals) as instance `inst` of the running sweep in place of what it was: mapped as at the
+// beginning (map_assumptions), base_assump / base_off / base_src rewritten, the instance open again with no verdict and
+// an empty core.  The workers hear of it through sweep_retarget().
+void sweep_repose(mi355sat& s, Sweep& sw, uint32_t inst, const std::vector<int32_t>& lits) {
+    std::vector<int32_t> a_int;
+    std::vector<uint64_t> a_off;
+    std::vector<uint32_t> src;
+    map_assumptions(s, s.perm, s.n_vars, lits, {0, (uint64_t)lits.size()}, 1, a_int, a_off, src);
+    if (a_int.size() > s.L.assump_cap) throw HipErr{"reposed assumption list does not fit the slabs"};
+    const uint64_t b0 = sw.base_off[inst], b1 = sw.base_off[inst + 1];
+    sw.base_assump.erase(sw.base_assump.begin() + b0, sw.base_assump.begin() + b1);
+    sw.base_assump.insert(sw.base_assump.begin() + b0, a_int.begin(), a_int.end());
+    sw.base_src.erase(sw.base_src.begin() + b0, sw.base_src.begin() + b1);
+    sw.base_src.insert(sw.base_src.begin() + b0, src.begin(), src.end());
+    for (uint32_t i = inst + 1; i <= sw.n_instances; i++) sw.base_off[i] = sw.base_off[i] - (b1 - b0) + a_int.size();
+    sw.results[inst] = MI355SAT_INTERRUPTED;
+    sw.winner[inst] = -1;
+    sw.dropped[inst] = 0;
+    sw.core_flag[inst].assign(lits.size(), 0);
+}
+
+// After the instances of a round are posed: every worker that has a slab moves to one of them (rebalance_workers ->
+// ms_assign_kernel: new assumption list, MS_ST_RUNNING, back to level 0); the lists go where grow_workers takes them
+// from for the workers the ramp-up creates later.
+void sweep_retarget(mi355sat& s, Sweep& sw) {
+    sw.decided = 0;
+    for (uint32_t i = 0; i < sw.n_instances; i++) sw.decided += inst_open(sw, i) ? 0 : 1;
+    s.d_assump.upload(sw.base_assump.empty() ? std::vector<int32_t>{0} : sw.base_assump, s.stream);
+    s.d_assump_off.upload(sw.base_off, s.stream);
+    if (sw.sts.size() != s.n_workers) gather_states(s, sw.sts);
+    rebalance_workers(s, sw, /*all=*/true);
+    HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
+}
+
+inline int32_t device_literal(const mi355sat& s, int32_t d) {      // the walk of map_assumptions for one literal
+    int32_t l = to_internal(d);
+    while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
+    return 2 * (int32_t)s.perm[l >> 1] | (l & 1);
+}
+
+// What the models of SAT candidates say about the literals they did not assume: ms_core_model_kernel, one wave per
+// winner, on the stream after the slice and ahead of anything that rewrites a slab's assumptions (a SAT instance's winner
+// keeps its slab until sweep_retarget).  chunks[k] = the caller's literals winner k's candidate left out; falsified[k]
+// receives, per device literal its model falsifies, the positions in chunks[k] that map to it.
+int core_models(mi355sat& s, Sweep& sw, const std::vector<int32_t>& winners, const std::vector<std::vector<int32_t>>& chunks,
+                std::vector<std::vector<std::vector<uint32_t>>>& falsified, mi355sat_core_min_info& info) {
+    const uint32_t n = (uint32_t)winners.size();
+    const uint32_t out_words = std::max<uint32_t>(1, (s.L.assump_cap + 31) / 32);
+    std::vector<int32_t> lits, q;
+    std::vector<uint64_t> off{0}, q_off64;
+    std::vector<uint32_t> src;
+    for (const auto& c : chunks) { lits.insert(lits.end(), c.begin(), c.end()); off.push_back(lits.size()); }
+    map_assumptions(s, s.perm, s.n_vars, lits, off, n, q, q_off64, src);
+    std::vector<uint32_t> q_off(q_off64.begin(), q_off64.end());
+    for (uint32_t k = 0; k < n; k++)
+        if (q_off[k + 1] - q_off[k] > out_words * 32u || (uint32_t)winners[k] >= s.n_alloc) throw HipErr{"core minimisation: list out of range"};
+    sw.d_fw.upload(winners, s.stream);
+    sw.d_qlits.upload(q.empty() ? std::vector<int32_t>{0} : q, s.stream);
+    sw.d_qoff.upload(q_off, s.stream);
+    if (sw.d_fout.n < (size_t)n * out_words) sw.d_fout.alloc((size_t)n * out_words);
+    if (sw.d_fok.n < n) sw.d_fok.alloc(n);
+    hipLaunchKernelGGL(ms_core_model_kernel, dim3(n), dim3(MS_WAVE), 0, s.stream, s.L, (const char*)s.d_slabs.p, (const int32_t*)sw.d_fw.p,
+                       (const int32_t*)sw.d_qlits.p, (const uint32_t*)sw.d_qoff.p, sw.d_fout.p, out_words, sw.d_fok.p);
+    HIPCHK(hipGetLastError());
+    info.model_launches++;
+    std::vector<uint32_t> out((size_t)n * out_words);
+    std::vector<int32_t> ok(n);
+    HIPCHK(hipMemcpyAsync(out.data(), sw.d_fout.p, sizeof(uint32_t) * out.size(), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(ok.data(), sw.d_fok.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    falsified.assign(n, {});
+    for (uint32_t k = 0; k < n; k++) {
+        if (!ok[k]) { set_error(&s, "device solver internal error (a SAT worker's slab is no model)"); return MI355SAT_ERR_STATE; }
+        const uint32_t b0 = q_off[k], nb = q_off[k + 1] - b0;
+        for (uint32_t i = 0; i < nb; i++) {
+            if (!((out[(size_t)k * out_words + i / 32] >> (i % 32)) & 1u)) continue;
+            std::vector<uint32_t> pos;
+            for (uint32_t p = src[b0 + i]; p < chunks[k].size(); p++)       // (src: the first position that maps to it)
+                if (device_literal(s, chunks[k][p]) == q[b0 + i]) pos.push_back(p);
+            falsified[k].push_back(pos);
+        }
+    }
+    return 0;
+}
+
+// The loop.  K: the working core (caller's literals, in the caller's order), crit[i]: K[i] is proved critical (formula
+// AND K without K[i] is SAT - which it stays for every later K, a subset).  Invariant: formula AND K is UNSAT.  A round
+// splits the literals not yet critical into chunks and poses K without chunk j as candidate j, at most N = min(64,
+// workers) of them.  UNSAT: its final-conflict core F (a subset of K without the chunk) becomes K; crit stays inside F.
+// SAT: the model falsifies a non-empty set D inside the chunk; |D| = 1 makes that literal critical.  A round of SAT
+// answers without a new critical literal halves the chunk size; at size 1 every SAT answer is a critical literal.  So
+// every round shrinks K, grows crit or halves the chunk size: the loop ends, with K = crit (irreducible), or on the
+// conflict budget / an interrupt with a K that is still a core.
+int minimize_search(mi355sat& s, std::vector<int32_t>& K, int64_t budget, mi355sat_core_min_info& info) {
+    uint32_t N = std::min<uint32_t>(64, fleet_size(s));
+    if (s.core_min_round) N = std::min(N, s.core_min_round);
+    N = (uint32_t)std::min<size_t>(N, K.size());
+    const std::vector<int32_t> K0 = K;
+    std::vector<uint8_t> crit(K.size(), 0);
+    uint64_t c = UINT64_MAX;              // chunk size of the round before (what a halving halves)
+    Sweep sw;
+    sw.cores = true;
+    bool begun = false, stop = false;
+    int rc = 0;
+    while (!rc) {
+        std::vector<uint32_t> open;       // positions in K not yet critical
+        for (uint32_t i = 0; i < K.size(); i++) if (!crit[i]) open.push_back(i);
+        if (open.empty()) { info.minimal = 1; break; }
+        if (stop) break;
+        // chunks: the whole of `open` in m even parts if that makes them no larger than c, else its first m * c literals
+        const uint32_t m = (uint32_t)std::min<size_t>(N, open.size());
+        const uint64_t even = (open.size() + m - 1) / m;
+        std::vector<std::vector<uint32_t>> chunk(m);
+        if (even <= c) c = even;
+        for (uint32_t j = 0; j < m; j++) {
+            const size_t a = even <= c ? open.size() * j / m : (size_t)c * j, b = even <= c ? open.size() * (j + 1) / m : (size_t)c * (j + 1);
+            chunk[j].assign(open.begin() + a, open.begin() + b);
+        }
+        std::vector<std::vector<uint32_t>> cand(m);       // positions in K
+        std::vector<std::vector<int32_t>> cand_lits(m);
+        for (uint32_t j = 0; j < m; j++) {
+            std::vector<uint8_t> out(K.size(), 0);
+            for (uint32_t i : chunk[j]) out[i] = 1;
+            for (uint32_t i = 0; i < K.size(); i++) if (!out[i]) { cand[j].push_back(i); cand_lits[j].push_back(K[i]); }
+        }
+        if (!begun) {     // (m == N in the first round)
+            std::vector<int32_t> assump;
+            std::vector<uint64_t> assump_off{0};
+            for (uint32_t j = 0; j < m; j++) { assump.insert(assump.end(), cand_lits[j].begin(), cand_lits[j].end()); assump_off.push_back(assump.size()); }
+            begun = true;
+            rc = sweep_begin(s, sw, assump, assump_off, N, false, &K0);
+            if (rc) break;
+        } else {
+            for (uint32_t j = 0; j < m; j++) sweep_repose(s, sw, j, cand_lits[j]);
+            for (uint32_t j = m; j < N; j++) { sw.results[j] = MI355SAT_INTERRUPTED; sw.winner[j] = -1; sw.dropped[j] = 1; }
+            sweep_retarget(s, sw);
+        }
+        info.rounds++;
+        info.candidates += m;
+        // slices until the first UNSAT answer, or all answers
+        for (;;) {
+            bool any_unsat = false;
+            for (uint32_t j = 0; j < m; j++) any_unsat = any_unsat || sw.results[j] == MI355SAT_UNSAT;
+            if (any_unsat || sw.decided == N || !sw.active) break;
+            if (s.interrupted.load() || *s.stop_flag || (budget > 0 && (int64_t)sw.conflicts >= budget)) { stop = true; break; }
+            if ((rc = sweep_step(s, sw)) != 0) break;
+        }
+        if (rc) break;
+        // SAT answers: the chunk's one literal, or what the model falsifies of it
+        uint32_t n_sat = 0, new_crit = 0;
+        std::vector<int32_t> winners;
+        std::vector<uint32_t> wj;
+        std::vector<std::vector<int32_t>> wchunks;
+        for (uint32_t j = 0; j < m; j++) {
+            if (sw.results[j] != MI355SAT_SAT) continue;
+            n_sat++;
+            if (chunk[j].size() == 1) { crit[chunk[j][0]] = 1; new_crit++; continue; }
+            winners.push_back(sw.winner[j]);
+            wj.push_back(j);
+            wchunks.emplace_back();
+            for (uint32_t i : chunk[j]) wchunks.back().push_back(K[i]);
+        }
+        info.candidates_sat += n_sat;
+        if (!winners.empty()) {
+            std::vector<std::vector<std::vector<uint32_t>>> falsified;
+            if ((rc = core_models(s, sw, winners, wchunks, falsified, info)) != 0) break;
+            for (size_t k = 0; k < winners.size(); k++) {
+                if (falsified[k].empty()) { set_error(&s, "device solver internal error (a model satisfies a refuted core)"); rc = MI355SAT_ERR_STATE; break; }
+                // several of the caller's literals on one device literal (repeats, equivalent literals): none is critical alone
+                if (falsified[k].size() != 1 || falsified[k][0].size() != 1) continue;
+                crit[chunk[wj[k]][falsified[k][0][0]]] = 1;
+                new_crit++;
+                info.critical_by_model++;
+            }
+            if (rc) break;
+        }
+        // UNSAT answers: the smallest of their cores is the new K
+        int best = -1;
+        std::vector<uint32_t> F;
+        for (uint32_t j = 0; j < m; j++) {
+            if (sw.results[j] != MI355SAT_UNSAT) continue;
+            info.candidates_unsat++;
+            std::vector<uint32_t> f;
+            for (size_t k = 0; k < cand[j].size(); k++) if (sw.core_flag[j][k]) f.push_back(cand[j][k]);
+            if (best < 0 || f.size() < F.size()) { best = (int)j; F.swap(f); }
+        }
+        if (best >= 0) {
+            std::vector<int32_t> K2;
+            std::vector<uint8_t> crit2, in(K.size(), 0);
+            for (uint32_t i : F) { in[i] = 1; K2.push_back(K[i]); crit2.push_back(crit[i]); }
+            for (uint32_t i = 0; i < K.size(); i++)
+                if (crit[i] && !in[i]) { set_error(&s, "device solver internal error (a core without a critical literal)"); rc = MI355SAT_ERR_STATE; }
+            if (rc) break;
+            K.swap(K2);
+            crit.swap(crit2);
+        } else if (!stop && new_crit == 0) c = std::max<uint64_t>(1, c / 2);
+    }
+    info.conflicts = sw.conflicts;
+    if (begun) sweep_end(s, sw);
+    else consume_interrupt(s);
+    return rc;
+}
+
+// core: the handle's core to minimise in place; minimal: its cached flag.  Returns 0 or a negative error.
+int minimize_core_impl(mi355sat* s, std::vector<int32_t>& core, bool& minimal, int64_t conflict_budget, mi355sat_core_min_info* out) {
+    mi355sat_core_min_info info{};
+    info.size_before = info.size_after = core.size();
+    const double t0 = now_s();
+    int rc = 0;
+    if (s->interrupted.load()) consume_interrupt(*s);                 // stopped at once: the core as it is
+    else if (minimal || core.empty()) { info.minimal = 1; minimal = true; }
+    else if (core.size() == 1 && s->sat_clauses == s->offs.size()) { info.minimal = 1; minimal = true; }   // the formula alone has a model
+    else {
+        s->inc.resident = false;                                      // "another search in between" for the warm mode
+        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
+        const mi355sat_opts opts = s->opts;
+        const mi355sat_stats_t st0 = s->stats;                        // (what describes the caller's last solve stays: below)
+        std::string proof_path;
+        proof_path.swap(s->proof_path);                               // the proof of the solve is closed: nothing is logged
+        s->opts.cube_split = 0;                                       // candidates are whole instances, one core each
+        std::vector<int32_t> K = core;
+        try {
+            HIPCHK(hipSetDevice(s->device));
+            rc = minimize_search(*s, K, conflict_budget, info);
+        } catch (HipErr& he) {
+            s->err = he.msg;
+            rc = MI355SAT_ERR_HIP;
+        } catch (std::bad_alloc&) {
+            s->err = "out of host memory";
+            rc = MI355SAT_ERR_OOM;
+        }
+        s->opts = opts;
+        s->proof_path.swap(proof_path);
+        // the simplification counters and the fleet size are those of the caller's last solve / batch, not of this upload
+        s->stats.simp_units = st0.simp_units; s->stats.simp_equivalences = st0.simp_equivalences;
+        s->stats.simp_clauses_removed = st0.simp_clauses_removed; s->stats.simp_eliminated = st0.simp_eliminated;
+        s->stats.workers = st0.workers;
+        if (!rc) {
+            core.swap(K);
+            minimal = info.minimal != 0;
+            info.size_after = core.size();
+        }
+        s->stats.solve_seconds += now_s() - t0;
+    }
+    info.seconds = now_s() - t0;
+    if (out) *out = info;
+    return rc;
+}
+
 }  // namespace
 
 struct SweepHolder { Sweep sw; mi355sat_stats_t base; };
@@ -2568,6 +2844,30 @@ int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap,
     return copy_core(s, s->batch_cores[instance], out, cap, n);
 }
 
+int mi355sat_minimize_core(mi355sat* s, int64_t conflict_budget, mi355sat_core_min_info* out) {
+    if (!s || conflict_budget < 0) return MI355SAT_ERR_ARG;
+    if (!s->core_valid || s->sweep) { s->err = "no core to minimise: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    return minimize_core_impl(s, s->core, s->core_minimal, conflict_budget, out);
+}
+
+int mi355sat_minimize_core_of(mi355sat* s, uint64_t instance, int64_t conflict_budget, mi355sat_core_min_info* out) {
+    if (!s || conflict_budget < 0) return MI355SAT_ERR_ARG;
+    if (instance >= s->batch_core_valid.size() || !s->batch_core_valid[instance] || s->sweep) {
+        s->err = "no core to minimise: instance out of range or not UNSAT in the last solve_batch()";
+        return instance >= s->batch_core_valid.size() && !s->batch_core_valid.empty() ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
+    }
+    bool minimal = s->batch_core_minimal[instance] != 0;
+    const int rc = minimize_core_impl(s, s->batch_cores[instance], minimal, conflict_budget, out);
+    s->batch_core_minimal[instance] = minimal ? 1 : 0;
+    return rc;
+}
+
+int mi355sat_debug_core_min_round(mi355sat* s, uint32_t max_candidates) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->core_min_round = max_candidates;
+    return 0;
+}
+
 // ---- phase hints: kept in the caller's variables; the next cold start (or a warm one, if they changed) applies them
 static int set_hint(mi355sat* s, uint64_t v, int8_t h) {      // v 1-based
     mi355sat::Phases& ph = s->ph;
@@ -2660,6 +2960,7 @@ int mi355sat_solve(mi355sat* s) {
     assump.swap(s->assumps);     // IPASIR: the assumptions hold for this solve only, whatever it returns
     s->core.clear();
     s->core_valid = false;
+    s->core_minimal = false;
     if (!s->pending.empty()) { s->err = "solve() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
     const double t0 = now_s();
     int result;
@@ -2686,7 +2987,7 @@ int mi355sat_solve(mi355sat* s) {
         s->err = "out of host memory";
         return MI355SAT_ERR_OOM;
     }
-    if (result == MI355SAT_SAT) s->stats.n_sat++;
+    if (result == MI355SAT_SAT) { s->stats.n_sat++; s->sat_clauses = s->offs.size(); }
     else if (result == MI355SAT_UNSAT) s->stats.n_unsat++;
     else s->stats.n_terminated++;
     s->stats.solve_seconds += now_s() - t0;
@@ -2706,17 +3007,19 @@ int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* as
         std::vector<int32_t> results, winner;
         s->batch_cores.clear();
         s->batch_core_valid.clear();
+        s->batch_core_minimal.clear();
         std::vector<std::vector<int32_t>> cores;
         int rc = run_search(*s, assump, aoff, (uint32_t)n_instances, results, winner, stop_at_first != 0, &cores);
         if (rc) { s->stats.solve_seconds += now_s() - t0; return rc; }
         s->batch_models.assign(n_instances, {});
         s->batch_cores.swap(cores);
         s->batch_core_valid.assign(n_instances, 0);
+        s->batch_core_minimal.assign(n_instances, 0);
         for (uint64_t i = 0; i < n_instances; i++) {
             results_out[i] = results[i];
             s->batch_core_valid[i] = results[i] == MI355SAT_UNSAT;
             if (results[i] == MI355SAT_SAT && winner[i] >= 0) fetch_model(*s, (uint32_t)winner[i], s->batch_models[i], s->max_var);
-            if (results[i] == MI355SAT_SAT) s->stats.n_sat++;
+            if (results[i] == MI355SAT_SAT) { s->stats.n_sat++; s->sat_clauses = s->offs.size(); }
             else if (results[i] == MI355SAT_UNSAT) s->stats.n_unsat++;
             else s->stats.n_terminated++;
         }

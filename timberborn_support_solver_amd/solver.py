@@ -94,6 +94,16 @@ class Mi355SatPhaseInfo(ctypes.Structure):   # mi355sat_phase_info (test hook)
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatCoreMinInfo(ctypes.Structure):   # mi355sat_core_min_info
+    _fields_ = [("size_before", ctypes.c_uint64), ("size_after", ctypes.c_uint64), ("minimal", ctypes.c_int32),
+                ("rounds", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("candidates", "candidates_unsat", "candidates_sat", "critical_by_model",
+                                               "model_launches", "conflicts")] + [("seconds", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
     NONE = 0
     FIRST = 1
@@ -134,6 +144,9 @@ def _bind(L):
     L.mi355sat_failed.argtypes = [vp, ctypes.c_int32]
     L.mi355sat_core.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.mi355sat_core_of.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_minimize_core.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(Mi355SatCoreMinInfo)]
+    L.mi355sat_minimize_core_of.argtypes = [vp, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Mi355SatCoreMinInfo)]
+    L.mi355sat_debug_core_min_round.argtypes = [vp, ctypes.c_uint32]
     L.mi355sat_solve_batch.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_int]
     L.mi355sat_sweep_begin.argtypes = [vp, vp, vp, ctypes.c_uint64]
     L.mi355sat_sweep_step.argtypes = [vp, vp, vp]
@@ -281,6 +294,26 @@ class Mi355Sat:
     def core_of(self, instance):
         """The same for an Unsat instance of the last solve_batch()."""
         return self._core(self._L.mi355sat_core_of, instance)
+
+    def minimize_core(self, conflict_budget=0):
+        """After solve() returned Unsat: shrink the core until no literal can be left out (deletion by rounds of
+        candidates, side by side on the device: include/mi355sat.h); core() / failed() answer with the new core.
+        conflict_budget > 0 bounds the conflicts summed over workers.  Returns mi355sat_core_min_info as a dict; its
+        "minimal" is 0 if the budget or an interrupt ended the call early (the core is still a core then)."""
+        info = Mi355SatCoreMinInfo()
+        self._check(self._L.mi355sat_minimize_core(self._h, int(conflict_budget), ctypes.byref(info)), "minimize_core")
+        return info.as_dict()
+
+    def minimize_core_of(self, instance, conflict_budget=0):
+        """The same for an Unsat instance of the last solve_batch(); core_of(instance) answers with the new core."""
+        info = Mi355SatCoreMinInfo()
+        self._check(self._L.mi355sat_minimize_core_of(self._h, int(instance), int(conflict_budget), ctypes.byref(info)),
+                    "minimize_core_of")
+        return info.as_dict()
+
+    def debug_core_min_round(self, max_candidates=0):
+        """Test hook: at most max_candidates candidates per round of minimize_core (0 = the default)."""
+        self._check(self._L.mi355sat_debug_core_min_round(self._h, int(max_candidates)), "debug_core_min_round")
 
     # ---- phase hints (rustsat PhaseLit's place; seeded, not forced: include/mi355sat.h)
     def phase(self, lit):
