@@ -340,6 +340,13 @@ struct SlabBuf {
 // One eliminated variable: literal x of it and the clauses (elim_lits[begin, end), -1 terminated, x included) that held x.
 struct MsElim { int32_t x; uint32_t begin, end; };
 
+// A failed-assumption core: caller's literals, in the order of the caller's assumption list.  valid: the answer it belongs
+// to was UNSAT and still stands; minimal: mi355sat_minimize_core proved it irreducible (it is not minimised again).
+struct Core {
+    std::vector<int32_t> lits;
+    bool valid = false, minimal = false;
+};
+
 struct mi355sat {
     mi355sat_opts opts{};
     int device = 0;
@@ -395,18 +402,12 @@ struct mi355sat {
     std::vector<MsElim> elims;                 // variables eliminated before search and the clauses that rebuild their values
     std::vector<int32_t> elim_lits;
     struct SweepHolder* sweep = nullptr;        // stepwise sweep in progress (mi355sat_sweep_*)
-    // IPASIR assumptions (mi355sat_assume) of the next solve(), and the failed-assumption cores: caller's literals, in the
-    // order of the caller's assumption list
+    // IPASIR assumptions (mi355sat_assume) of the next solve(), and the failed-assumption cores
     std::vector<int32_t> assumps;
-    std::vector<int32_t> core;                 // of the last solve(), valid after UNSAT until the next add / assume / solve
-    bool core_valid = false;
-    std::vector<std::vector<int32_t>> batch_cores;   // of the last solve_batch(), per instance
-    std::vector<uint8_t> batch_core_valid;
-    // core minimisation (mi355sat_minimize_core): a core it proved irreducible is not minimised again (the flags fall with
-    // the cores); the formula is known to be satisfiable while no clause was added since a SAT answer; test hook
-    // (mi355sat_debug_core_min_round): at most this many candidates per round, 0 = the default
-    bool core_minimal = false;
-    std::vector<uint8_t> batch_core_minimal;
+    Core core;                                 // of the last solve(), valid after UNSAT until the next add / assume / solve
+    std::vector<Core> batch_cores;             // of the last solve_batch(), per instance
+    // core minimisation (mi355sat_minimize_core): the formula is known to be satisfiable while no clause was added since
+    // a SAT answer; test hook (mi355sat_debug_core_min_round): at most this many candidates per round, 0 = the default
     uint64_t sat_clauses = UINT64_MAX;         // stats.n_clauses when a solve / batch last answered SAT
     uint32_t core_min_round = 0;
     // warm incremental solve (mi355sat_set_incremental): what the last mi355sat_solve() left on the device, and what was
@@ -471,9 +472,73 @@ struct Prepared {
     std::vector<int32_t> tern_owner;
 };
 
+inline uint64_t var_of(int32_t d) { return (uint64_t)(d < 0 ? -(int64_t)d : d); }      // |d|: a DIMACS literal's variable
 inline int32_t to_internal(int32_t d) { return d > 0 ? 2 * (d - 1) : 2 * (-d - 1) + 1; }
 inline int32_t to_device(const std::vector<uint32_t>& perm, int32_t d) {   // DIMACS literal -> device literal
     return d > 0 ? 2 * (int32_t)perm[d - 1] : 2 * (int32_t)perm[-d - 1] + 1;
+}
+// The same for a formula that went through the simplification - the one route of assumptions, clauses attached warm, phase
+// hints and imported records: the equivalent-literal substitution (which may flip the sign), then the device's variable
+// order (perm: s.perm once uploaded).  The caller has checked the range.  gone (may be null), per caller variable: resolved
+// away before the upload - such a representative has no device variable, and the answer is -1.
+inline int32_t device_literal(const mi355sat& s, const std::vector<uint32_t>& perm, int32_t d, const std::vector<uint8_t>* gone = nullptr) {
+    int32_t l = to_internal(d);
+    while ((size_t)(l >> 1) < s.subst.size() && s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
+    if (gone && (*gone)[l >> 1]) return -1;
+    return 2 * (int32_t)perm[l >> 1] | (l & 1);
+}
+
+// (warm incremental solve) What is on the device is no solve()'s to go on with: the next one starts cold, for this reason.
+// Whatever rewrites the slabs or changes what a worker's state depends on comes through here - a missed call is a wrong
+// warm start.
+inline void go_cold(mi355sat& s, int why) {
+    s.inc.resident = false;
+    s.inc.why_not = why;
+}
+
+// The one way an entry point of the C ABI runs code that may throw: nothing crosses the extern "C" boundary.  The body
+// returns the call's result; a HipErr becomes MI355SAT_ERR_HIP with its text, std::bad_alloc MI355SAT_ERR_OOM.  On the
+// device (all but GUARD_HOST) the handle's device is selected first; GUARD_TIMED adds the call's time to
+// stats.solve_seconds, whichever way it ends.
+enum GuardKind { GUARD_HOST, GUARD_DEVICE, GUARD_TIMED };
+template <class F>
+int guarded(mi355sat* s, GuardKind kind, F&& body) {
+    const double t0 = kind == GUARD_TIMED ? now_s() : 0;
+    int rc;
+    try {
+        if (kind != GUARD_HOST) HIPCHK(hipSetDevice(s->device));
+        rc = body();
+    } catch (HipErr& he) {
+        s->err = he.msg;
+        rc = MI355SAT_ERR_HIP;
+    } catch (std::bad_alloc&) {
+        s->err = "out of host memory";
+        rc = MI355SAT_ERR_OOM;
+    }
+    if (kind == GUARD_TIMED) s->stats.solve_seconds += now_s() - t0;
+    return rc;
+}
+
+// What in stats describes the caller's last solve / batch - what the simplification did to the formula, the fleet's size -
+// and not an upload made on the side (a running sweep's totals, core minimisation).
+inline void keep_last_solve_stats(mi355sat_stats_t& dst, const mi355sat_stats_t& src) {
+    dst.simp_units = src.simp_units; dst.simp_equivalences = src.simp_equivalences;
+    dst.simp_clauses_removed = src.simp_clauses_removed; dst.simp_eliminated = src.simp_eliminated;
+    dst.workers = src.workers;
+}
+
+inline void tally_answer(mi355sat& s, int result) {
+    if (result == MI355SAT_SAT) { s.stats.n_sat++; s.sat_clauses = s.offs.size(); }
+    else if (result == MI355SAT_UNSAT) s.stats.n_unsat++;
+    else s.stats.n_terminated++;
+}
+
+// A caller's lists (data[offsets[i] .. offsets[i + 1]) for i < n; offsets[0] need not be 0) as a copy with offsets from 0.
+inline void copy_lists(const int32_t* data, const uint64_t* offsets, uint64_t n, std::vector<int32_t>& out, std::vector<uint64_t>& off) {
+    off.assign(offsets, offsets + n + 1);
+    for (auto& o : off) o -= offsets[0];
+    out.clear();
+    if (off.back()) out.assign(data + offsets[0], data + offsets[n]);
 }
 
 // Variable order for the device: every per-variable array (the 2-bit assignment: 256 variables per
@@ -947,10 +1012,9 @@ void map_phases(mi355sat& s) {
     ph.info.dropped_eliminated = ph.info.dropped_fixed = ph.info.mapped = 0;
     for (size_t v = 0; v < ph.hint.size() && v < s.n_vars; v++) {
         if (!ph.hint[v]) continue;
-        int32_t l = 2 * (int32_t)v + (ph.hint[v] < 0 ? 1 : 0);
-        while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
-        if (gone[l >> 1]) { ph.info.dropped_eliminated++; continue; }
-        const uint32_t dv = s.perm[l >> 1];
+        const int32_t l = device_literal(s, s.perm, ph.hint[v] < 0 ? -(int32_t)(v + 1) : (int32_t)(v + 1), &gone);
+        if (l < 0) { ph.info.dropped_eliminated++; continue; }
+        const uint32_t dv = (uint32_t)(l >> 1);
         if (dv < ph.dev_fixed.size() && ph.dev_fixed[dv]) { ph.info.dropped_fixed++; continue; }
         bytes[dv] = (uint8_t)(1 + (l & 1));
     }
@@ -1486,38 +1550,49 @@ void keep_simplified_copy(mi355sat& s, const Formula& F) {
     s.kept_valid = true;
 }
 
-void accumulate_stats(mi355sat& s, const std::vector<MsState>& sts) {
+// The members of MsState that are running counters - a worker only ever adds to them, from the template on - as pairs
+// (a's, b's): the one list behind summing them over workers and taking a warm solve's share of them.  A counter added to
+// MsState goes here.
+template <class A, class B, class Op>
+void for_each_counter(A& a, B& b, Op op) {
+    op(a.n_steps, b.n_steps); op(a.n_redo, b.n_redo);
+    op(a.propagations, b.propagations); op(a.decisions, b.decisions); op(a.conflicts, b.conflicts); op(a.restarts, b.restarts);
+    op(a.reduce_dbs, b.reduce_dbs); op(a.n_watch, b.n_watch); op(a.n_cl_lit, b.n_cl_lit); op(a.n_move, b.n_move); op(a.n_enq, b.n_enq);
+    op(a.n_exported, b.n_exported); op(a.n_imported, b.n_imported); op(a.n_imported_units, b.n_imported_units);
+    op(a.slice_cycles, b.slice_cycles); op(a.learnt_total, b.learnt_total); op(a.learnt_lits_total, b.learnt_lits_total);
+    op(a.n_vivified, b.n_vivified); op(a.n_viv_lits, b.n_viv_lits); op(a.n_rephase, b.n_rephase);
+    op(a.n_import_skipped, b.n_import_skipped); op(a.n_forced_imports, b.n_forced_imports);
+    for (int i = 0; i < 16; i++) op(a.prof[i], b.prof[i]);
+}
+
+// Adds the workers' counters to the handle's stats.  bcp_times (mi355sat_propagate_batch with `repeat`): sts are the
+// counters of one run of that many identical ones, and the BCP traffic counters stand for all of them.
+void accumulate_stats(mi355sat& s, const std::vector<MsState>& sts, uint64_t bcp_times = 1) {
     mi355sat_stats_t& o = s.stats;
+    MsState t{};                 // the counters summed over the workers
     uint64_t learnts = 0, llits = 0;
-    uint64_t props = 0, dec = 0, confl = 0, rest = 0, red = 0, nw = 0, ncl = 0, nm = 0, ne = 0, steps = 0, redo = 0;
     for (auto& st : sts) {
-        steps += st.n_steps; redo += st.n_redo;
-        props += st.propagations; dec += st.decisions; confl += st.conflicts; rest += st.restarts;
-        red += st.reduce_dbs; nw += st.n_watch; ncl += st.n_cl_lit; nm += st.n_move; ne += st.n_enq;
+        for_each_counter(t, st, [](auto& sum, const auto& x) { sum += x; });
         learnts += st.n_learnts; llits += st.lc_lits_n;
     }
-    o.propagations += props; o.decisions += dec; o.conflicts += confl; o.restarts += rest; o.reduce_dbs += red;
-    o.n_deq += props; o.n_watch += nw; o.n_cl_lit += ncl; o.n_move += nm; o.n_enq += ne;
+    o.propagations += t.propagations * bcp_times; o.n_deq += t.propagations * bcp_times; o.n_watch += t.n_watch * bcp_times;
+    o.n_cl_lit += t.n_cl_lit * bcp_times; o.n_move += t.n_move * bcp_times; o.n_enq += t.n_enq * bcp_times;
+    o.decisions += t.decisions; o.conflicts += t.conflicts; o.restarts += t.restarts; o.reduce_dbs += t.reduce_dbs;
     o.learnts = learnts; o.learnt_literals = llits;
-    o.bcp_steps += steps; o.bcp_requeued += redo;
-    uint64_t exported = 0, imported = 0, imported_units = 0;
-    for (auto& st : sts) { exported += st.n_exported; imported += st.n_imported; imported_units += st.n_imported_units; }
-    o.shared_exported += exported; o.shared_imported += imported; o.shared_imported_units += imported_units;
+    o.bcp_steps += t.n_steps; o.bcp_requeued += t.n_redo;
+    o.shared_exported += t.n_exported; o.shared_imported += t.n_imported; o.shared_imported_units += t.n_imported_units;
     s.heur = mi355sat_heuristics_info{};
-    for (auto& st : sts) {
-        s.heur.n_vivified += st.n_vivified; s.heur.n_viv_lits += st.n_viv_lits; s.heur.n_rephase += st.n_rephase;
-        s.heur.import_skipped += st.n_import_skipped; s.heur.forced_imports += st.n_forced_imports;
-    }
-    uint64_t prof[16] = {0}, cyc = 0;
-    for (auto& st : sts) { for (int i = 0; i < 16; i++) prof[i] += st.prof[i]; cyc += st.slice_cycles; }
+    s.heur.n_vivified = t.n_vivified; s.heur.n_viv_lits = t.n_viv_lits; s.heur.n_rephase = t.n_rephase;
+    s.heur.import_skipped = t.n_import_skipped; s.heur.forced_imports = t.n_forced_imports;
+    const uint64_t* prof = t.prof;
+    const uint64_t cyc = t.slice_cycles;
     if (prof[0] && s.opts.verbose) {
         static const char* nm[] = {"offsets", "binary", "ternary", "long", "close", "analyze", "backjump+learn", "decide", "reduce"};
         fprintf(stderr, "[mi355sat] phase cycle shares of %.3e worker-cycles:", (double)cyc);
         for (int i = 0; i < 9; i++) fprintf(stderr, " %s=%.1f%%", nm[i], 100.0 * (double)prof[i] / (double)cyc);
-        uint64_t confl = 0, ll = 0, lt = 0;
-        for (auto& st : sts) { confl += st.conflicts; ll += st.learnt_lits_total; lt += st.learnt_total; }
+        const uint64_t confl = t.conflicts;
         fprintf(stderr, "; resolution steps per conflict %.1f, learnt clause %.1f literals", (double)prof[9] / (double)std::max<uint64_t>(1, confl),
-                (double)ll / (double)std::max<uint64_t>(1, lt));
+                (double)t.learnt_lits_total / (double)std::max<uint64_t>(1, t.learnt_total));
         fprintf(stderr, "; of analyze: recursive minimisation %.1f%%, local %.1f%%; %.1f nodes per call, %.2f calls per conflict\n",
                 100.0 * (double)prof[10] / (double)cyc, 100.0 * (double)prof[11] / (double)cyc,
                 (double)prof[12] / (double)std::max<uint64_t>(1, prof[13]), (double)prof[13] / (double)std::max<uint64_t>(1, confl));
@@ -1759,6 +1834,49 @@ struct Sweep {
     bool keep_warm = false;
     std::vector<MsState> counters0;
     uint64_t conflicts0 = 0;
+
+    // Instance `inst` is posed (anew): open, no verdict, an empty core over its n_assumps entries of the caller's list.
+    void pose(uint32_t inst, uint64_t n_assumps) {
+        results[inst] = MI355SAT_INTERRUPTED;
+        winner[inst] = -1;
+        dropped[inst] = 0;
+        if (cores) core_flag[inst].assign(n_assumps, 0);
+    }
+    // A sweep over n instances begins (assump_off: the caller's lists): nothing decided, no kernel time, no counters
+    // taken over.  `cores` is the caller's to set before, `split` and the per-worker arrays (place_workers) follow once
+    // the fleet is known.
+    void reset(uint32_t n, bool first_only, const std::vector<uint64_t>& assump_off) {
+        n_instances = n;
+        stop_at_first = first_only;
+        decided = 0;
+        active = split = false;
+        n_moved = 0;
+        ramp_ms = 0;
+        counters0.clear();
+        conflicts0 = 0;
+        results.resize(n);
+        winner.resize(n);
+        dropped.resize(n);
+        core_flag.assign(cores ? n : 0, {});
+        for (uint32_t i = 0; i < n; i++) pose(i, assump_off[i + 1] - assump_off[i]);
+    }
+    // Worker w of W starts on instance w % n_instances, its cube that instance's list (base_assump / base_off); with cube
+    // splitting only the first worker of an instance is busy, the others wait for a cube to steal.
+    void place_workers(uint32_t W) {
+        w_inst.assign(W, 0);
+        w_cube.assign(W, {});
+        w_busy.assign(W, 0);
+        w_conf0.assign(W, 0);
+        open.assign(n_instances, 0);
+        for (uint32_t w = 0; w < W; w++) {
+            const uint32_t inst = w % n_instances;
+            w_inst[w] = (int32_t)inst;
+            if (split && w >= n_instances) continue;
+            w_busy[w] = 1;
+            w_cube[w].assign(base_assump.begin() + base_off[inst], base_assump.begin() + base_off[inst + 1]);
+            open[inst]++;
+        }
+    }
 };
 
 // Caller's assumption lists -> device literals: equivalent-literal substitution, then the device's variable order (perm);
@@ -1773,11 +1891,9 @@ void map_assumptions(const mi355sat& s, const std::vector<uint32_t>& perm, uint3
     std::vector<uint32_t> stamp(2 * (size_t)n_vars, 0);
     for (uint32_t i = 0; i < n_instances; i++) {
         for (uint64_t k = assump_off[i]; k < assump_off[i + 1]; k++) {
-            int32_t d = assump[k];
-            if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > n_vars) throw HipErr{"assumption literal out of range"};
-            int32_t l = to_internal(d);
-            while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);     // a variable replaced by an equivalent literal
-            l = 2 * (int32_t)perm[l >> 1] | (l & 1);
+            const int32_t d = assump[k];
+            if (d == 0 || var_of(d) > n_vars) throw HipErr{"assumption literal out of range"};
+            const int32_t l = device_literal(s, perm, d);
             if (stamp[l] == i + 1) continue;
             stamp[l] = i + 1;
             a_int.push_back(l);
@@ -1801,11 +1917,12 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         Formula F;
         normalise(s, F);
         F.log_proof = !s.proof_path.empty();
-        for (int32_t d : assump)
-            if (d != 0 && (uint64_t)(d < 0 ? -(int64_t)d : d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
-        if (keep)
-            for (int32_t d : *keep)
-                if (d != 0 && (uint64_t)(d < 0 ? -(int64_t)d : d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
+        auto freeze = [&](const std::vector<int32_t>& list) {
+            for (int32_t d : list)
+                if (d != 0 && var_of(d) <= F.nv) F.frozen_lits.push_back(to_internal(d));
+        };
+        freeze(assump);
+        if (keep) freeze(*keep);
         simplify_formula(s, F);
         if (s.keep_simplified) keep_simplified_copy(s, F);
         build_csr(s, F, /*units_propagated=*/true, P);
@@ -1822,17 +1939,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         if (n_instances != 1) throw HipErr{"a proof can only be logged for a plain solve()"};
         proof_open(s);
     }
-    sw.n_instances = n_instances;
-    sw.stop_at_first = stop_at_first;
-    sw.decided = 0;
-    sw.active = false;
-    sw.results.assign(n_instances, MI355SAT_INTERRUPTED);
-    sw.winner.assign(n_instances, -1);
-    sw.dropped.assign(n_instances, 0);
-    sw.n_moved = 0;
-    sw.ramp_ms = 0;
-    sw.core_flag.assign(sw.cores ? n_instances : 0, {});
-    for (size_t i = 0; i < sw.core_flag.size(); i++) sw.core_flag[i].assign(assump_off[i + 1] - assump_off[i], 0);
+    sw.reset(n_instances, stop_at_first, assump_off);
     s.ph.on_device = false;              // (the mapping of the hints on the device was the last upload's)
     if (P.unsat) {
         std::fill(sw.results.begin(), sw.results.end(), MI355SAT_UNSAT);
@@ -1877,24 +1984,10 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     for (int32_t l : P.units) s.ph.dev_fixed[l >> 1] = 1;
     apply_phases(s, /*warm=*/false);     // after the customisation: a hint outranks opts.phase_mix
     HIPCHK(hipStreamSynchronize(s.stream));
-    const uint32_t W = s.n_workers;
-    s.stats.workers = W;
+    s.stats.workers = s.n_workers;
     sw.base_assump = a_int;
     sw.base_off = a_off;
-    sw.w_inst.assign(W, 0);
-    sw.w_cube.assign(W, {});
-    sw.w_busy.assign(W, 0);
-    sw.w_conf0.assign(W, 0);
-    sw.open.assign(n_instances, 0);
-    for (uint32_t w = 0; w < W; w++) {
-        uint32_t inst = w % n_instances;
-        sw.w_inst[w] = (int32_t)inst;
-        if (!sw.split || w < n_instances) {
-            sw.w_busy[w] = 1;
-            sw.w_cube[w].assign(a_int.begin() + a_off[inst], a_int.begin() + a_off[inst + 1]);
-            sw.open[inst]++;
-        }
-    }
+    sw.place_workers(s.n_workers);
     sw.active = true;
     return 0;
 }
@@ -2044,27 +2137,17 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
     HIPCHK(hipStreamSynchronize(s.stream));
 }
 
-// Failed assumptions of the workers in fw, which came back MS_ST_REFUTED from the slice just gathered: ms_final_kernel,
-// on the stream ahead of anything that rewrites a slab's assumptions (rebalance_workers, schedule_cubes, customize).  The
-// kernel reports indices into the worker's (deduplicated) assumption list: those below its instance's own count map back
-// to the caller's list through base_src; split literals (cube_split) drop out - the cubes of an instance are the leaves
-// of a complete split tree, so the union of their cores restricted to the instance's assumptions is a core of it.
-int final_cores(mi355sat& s, Sweep& sw, const std::vector<int32_t>& fw) {
-    const uint32_t n = (uint32_t)fw.size();
-    const uint32_t out_words = std::max<uint32_t>(1, (s.L.assump_cap + 31) / 32);
-    const uint32_t mwords = (s.n_vars + 31) / 32;
-    const bool lds = s.opts.lds_val >= 0 && 4ull * mwords <= 48 * 1024;   // the marks in LDS, or a scratch row per workgroup
-    sw.d_fw.upload(fw, s.stream);
+// What ms_final_kernel and ms_core_model_kernel answer with: per wave k of n a row of bits (sw.d_fout, out_words words each:
+// one bit per entry of a worker's assumption list) and a flag that the row is sound (sw.d_fok).  Grows the two buffers,
+// has the caller launch its kernel on the stream, reads both back and hands over every set bit i of every row k, in
+// increasing order; a row that is not sound ends it with MI355SAT_ERR_STATE and the caller's text.
+inline uint32_t bit_row_words(const mi355sat& s) { return std::max<uint32_t>(1, (s.L.assump_cap + 31) / 32); }
+template <class Launch, class Bit>
+int read_bit_rows(mi355sat& s, Sweep& sw, uint32_t n, const char* not_ok, Launch launch, Bit bit) {
+    const uint32_t out_words = bit_row_words(s);
     if (sw.d_fout.n < (size_t)n * out_words) sw.d_fout.alloc((size_t)n * out_words);
     if (sw.d_fok.n < n) sw.d_fok.alloc(n);
-    if (lds) {
-        hipLaunchKernelGGL(ms_final_kernel<true>, dim3(n), dim3(MS_WAVE), 4 * mwords, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
-                           (const int32_t*)sw.d_fw.p, (uint32_t*)nullptr, sw.d_fout.p, out_words, sw.d_fok.p);
-    } else {
-        if (sw.d_fscratch.n < (size_t)n * std::max<uint32_t>(mwords, 1)) sw.d_fscratch.alloc((size_t)n * std::max<uint32_t>(mwords, 1));
-        hipLaunchKernelGGL(ms_final_kernel<false>, dim3(n), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
-                           (const int32_t*)sw.d_fw.p, sw.d_fscratch.p, sw.d_fout.p, out_words, sw.d_fok.p);
-    }
+    launch(out_words);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> out((size_t)n * out_words);
     std::vector<int32_t> ok(n);
@@ -2072,13 +2155,37 @@ int final_cores(mi355sat& s, Sweep& sw, const std::vector<int32_t>& fw) {
     HIPCHK(hipMemcpyAsync(ok.data(), sw.d_fok.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s.stream));
     HIPCHK(hipStreamSynchronize(s.stream));
     for (uint32_t k = 0; k < n; k++) {
-        if (!ok[k]) { set_error(&s, "device solver internal error (final conflict analysis)"); return MI355SAT_ERR_STATE; }
-        const uint32_t inst = (uint32_t)sw.w_inst[fw[k]];
-        const uint64_t b0 = sw.base_off[inst], nb = sw.base_off[inst + 1] - b0;
-        for (uint64_t i = 0; i < nb; i++)
-            if ((out[(size_t)k * out_words + i / 32] >> (i % 32)) & 1u) sw.core_flag[inst][sw.base_src[b0 + i]] = 1;
+        if (!ok[k]) { set_error(&s, not_ok); return MI355SAT_ERR_STATE; }
+        for (uint32_t i = 0; i < 32 * out_words; i++)
+            if ((out[(size_t)k * out_words + i / 32] >> (i % 32)) & 1u) bit(k, i);
     }
     return 0;
+}
+
+// Failed assumptions of the workers in fw, which came back MS_ST_REFUTED from the slice just gathered: ms_final_kernel,
+// on the stream ahead of anything that rewrites a slab's assumptions (rebalance_workers, schedule_cubes, customize).  The
+// kernel reports indices into the worker's (deduplicated) assumption list: those below its instance's own count map back
+// to the caller's list through base_src; split literals (cube_split) drop out - the cubes of an instance are the leaves
+// of a complete split tree, so the union of their cores restricted to the instance's assumptions is a core of it.
+int final_cores(mi355sat& s, Sweep& sw, const std::vector<int32_t>& fw) {
+    const uint32_t n = (uint32_t)fw.size();
+    const uint32_t mwords = (s.n_vars + 31) / 32;
+    const bool lds = s.opts.lds_val >= 0 && 4ull * mwords <= 48 * 1024;   // the marks in LDS, or a scratch row per workgroup
+    sw.d_fw.upload(fw, s.stream);
+    return read_bit_rows(s, sw, n, "device solver internal error (final conflict analysis)", [&](uint32_t out_words) {
+        if (lds) {
+            hipLaunchKernelGGL(ms_final_kernel<true>, dim3(n), dim3(MS_WAVE), 4 * mwords, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
+                               (const int32_t*)sw.d_fw.p, (uint32_t*)nullptr, sw.d_fout.p, out_words, sw.d_fok.p);
+        } else {
+            if (sw.d_fscratch.n < (size_t)n * std::max<uint32_t>(mwords, 1)) sw.d_fscratch.alloc((size_t)n * std::max<uint32_t>(mwords, 1));
+            hipLaunchKernelGGL(ms_final_kernel<false>, dim3(n), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, (const char*)s.d_slabs.p,
+                               (const int32_t*)sw.d_fw.p, sw.d_fscratch.p, sw.d_fout.p, out_words, sw.d_fok.p);
+        }
+    }, [&](uint32_t k, uint32_t i) {
+        const uint32_t inst = (uint32_t)sw.w_inst[fw[k]];
+        const uint64_t b0 = sw.base_off[inst];
+        if (i < sw.base_off[inst + 1] - b0) sw.core_flag[inst][sw.base_src[b0 + i]] = 1;
+    });
 }
 
 // ---- warm incremental solve ----------------------------------------------------------------------------------------
@@ -2104,13 +2211,9 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
     if (!I.resident) return I.why_not;
     // the caller's literal on the device, or the reason why it has none
     auto map_lit = [&](int32_t d, int32_t& out) -> int {
-        const uint64_t v = (uint64_t)(d < 0 ? -(int64_t)d : d);
-        if (v > s.n_vars) return MI355SAT_COLD_NEW_VAR;
-        int32_t l = to_internal(d);
-        while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
-        if (I.eliminated[l >> 1]) return MI355SAT_COLD_ELIMINATED;
-        out = 2 * (int32_t)s.perm[l >> 1] | (l & 1);
-        return 0;
+        if (var_of(d) > s.n_vars) return MI355SAT_COLD_NEW_VAR;
+        out = device_literal(s, s.perm, d, &I.eliminated);
+        return out < 0 ? MI355SAT_COLD_ELIMINATED : 0;
     };
     int32_t l = 0;
     for (int32_t d : assump) if (int why = map_lit(d, l)) return why;
@@ -2153,29 +2256,14 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
     I.pinned += pinned;
     I.pinned_lits += pinned_lits;
     I.n_clauses = nc;
-    sw.n_instances = 1;
-    sw.stop_at_first = true;
-    sw.decided = 0;
-    sw.active = false;
-    sw.results.assign(1, MI355SAT_INTERRUPTED);
-    sw.winner.assign(1, -1);
-    sw.dropped.assign(1, 0);
-    sw.n_moved = 0;
-    sw.ramp_ms = 0;
-    sw.split = false;
-    sw.core_flag.assign(sw.cores ? 1 : 0, std::vector<uint8_t>(assump.size(), 0));
+    sw.reset(1, /*first_only=*/true, assump_off);
     sw.base_src = base_src;
     sw.base_assump = a_int;
     sw.base_off = a_off;
     const uint32_t W = s.n_workers;
-    sw.w_inst.assign(W, 0);
-    sw.w_cube.assign(W, a_int);
-    sw.w_busy.assign(W, 1);
-    sw.w_conf0.assign(W, 0);
-    sw.open.assign(1, W);
+    sw.place_workers(W);         // (one instance: every worker on it)
     sw.counters0 = I.base;
     sw.counters0.resize(W, MsState{});
-    sw.conflicts0 = 0;
     I.info.resident_learnts = 0;
     for (const MsState& st : sw.counters0) { sw.conflicts0 += st.conflicts; I.info.resident_learnts += st.n_learnts; }
     I.info.attached_clauses += pinned;
@@ -2322,17 +2410,8 @@ void consume_interrupt(mi355sat& s) {
 void sweep_end(mi355sat& s, Sweep& sw) {
     if (sw.active && !sw.counters0.empty()) {   // a warm solve: the workers' counters ran on from the solve before
         std::vector<MsState> d = sw.sts;
-        for (size_t w = 0; w < d.size() && w < sw.counters0.size(); w++) {
-            const MsState& b = sw.counters0[w];
-            d[w].n_steps -= b.n_steps; d[w].n_redo -= b.n_redo; d[w].propagations -= b.propagations; d[w].decisions -= b.decisions;
-            d[w].conflicts -= b.conflicts; d[w].restarts -= b.restarts; d[w].reduce_dbs -= b.reduce_dbs; d[w].n_watch -= b.n_watch;
-            d[w].n_cl_lit -= b.n_cl_lit; d[w].n_move -= b.n_move; d[w].n_enq -= b.n_enq; d[w].n_exported -= b.n_exported;
-            d[w].n_imported -= b.n_imported; d[w].n_imported_units -= b.n_imported_units; d[w].slice_cycles -= b.slice_cycles;
-            d[w].learnt_total -= b.learnt_total; d[w].learnt_lits_total -= b.learnt_lits_total;
-            d[w].n_vivified -= b.n_vivified; d[w].n_viv_lits -= b.n_viv_lits; d[w].n_rephase -= b.n_rephase;
-            d[w].n_import_skipped -= b.n_import_skipped; d[w].n_forced_imports -= b.n_forced_imports;
-            for (int i = 0; i < 16; i++) d[w].prof[i] -= b.prof[i];
-        }
+        for (size_t w = 0; w < d.size() && w < sw.counters0.size(); w++)
+            for_each_counter(d[w], sw.counters0[w], [](auto& now, const auto& then) { now -= then; });
         accumulate_stats(s, d);
     } else if (sw.active) accumulate_stats(s, sw.sts);
     sw.active = false;
@@ -2345,11 +2424,7 @@ int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vecto
                uint32_t n_instances, std::vector<int32_t>& results, std::vector<int32_t>& winner, bool stop_at_first,
                std::vector<std::vector<int32_t>>* cores = nullptr, bool plain_solve = false) {
     mi355sat::Incremental& I = s.inc;
-    const bool incremental = plain_solve && I.on;
-    if (!incremental) {     // solve_batch, or the mode is off: today's path, and what is on the device is no solve()'s any more
-        I.resident = false;
-        I.why_not = plain_solve ? MI355SAT_COLD_FIRST : MI355SAT_COLD_OTHER_SEARCH;
-    }
+    const bool incremental = plain_solve && I.on;     // (else solve_batch, or the mode is off: always cold, nothing kept)
     if (incremental && I.refuted && s.proof_path.empty()) {     // the formula only grows: UNSAT with the empty core, no launch
         results.assign(1, MI355SAT_UNSAT);
         winner.assign(1, -1);
@@ -2361,38 +2436,38 @@ int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vecto
     Sweep sw;
     sw.cores = cores != nullptr;
     int rc = 0;
+    // 1. warm - on the workers the solve() before left - or cold: simplified, uploaded and replicated anew
     const int why = incremental ? warm_begin(s, sw, assump, assump_off) : MI355SAT_COLD_FIRST;
-    if (incremental && why == MI355SAT_COLD_NONE) I.info.warm_solves++;
+    const bool warm = incremental && why == MI355SAT_COLD_NONE;
+    sw.keep_warm = incremental && s.proof_path.empty() && s.opts.cube_split <= 0;    // (what a warm start takes, too)
+    bool uploaded = false;      // a cold start put workers on the device that the next solve() may go on with
+    if (warm) I.info.warm_solves++;
     else {
         if (incremental) {
             I.info.cold_solves++;
             I.info.last_cold_reason = why;
-            I.resident = false;
-            I.why_not = MI355SAT_COLD_FIRST;
-            sw.keep_warm = s.proof_path.empty() && s.opts.cube_split <= 0;
-            sw.counters0.clear();
-            sw.conflicts0 = 0;
         }
+        go_cold(s, plain_solve ? MI355SAT_COLD_FIRST : MI355SAT_COLD_OTHER_SEARCH);
         rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first);
-        if (sw.keep_warm && !rc) {
-            if (s.trivially_unsat) I.refuted = true;
-            else {      // uploaded: the next solve() may start from these workers
-                I.resident = true;
-                I.n_clauses = s.offs.size() - 1;
-                I.eliminated.assign(s.n_vars, 0);
-                for (const MsElim& e : s.elims) I.eliminated[e.x >> 1] = 1;
-                I.lits.clear();
-                I.offs.assign(1, 0);
-                I.pinned = I.pinned_lits = 0;
-            }
+        if (sw.keep_warm && !rc && s.trivially_unsat) I.refuted = true;
+        uploaded = sw.keep_warm && !rc && !s.trivially_unsat;
+        if (uploaded) {     // what these workers know: the formula as it stands, nothing attached
+            I.n_clauses = s.offs.size() - 1;
+            I.eliminated.assign(s.n_vars, 0);
+            for (const MsElim& e : s.elims) I.eliminated[e.x >> 1] = 1;
+            I.lits.clear();
+            I.offs.assign(1, 0);
+            I.pinned = I.pinned_lits = 0;
         }
     }
-    if (incremental && why == MI355SAT_COLD_NONE) sw.keep_warm = true;
+    // 2. search
     const bool searched = sw.active;
     while (!rc && !sweep_finished(s, sw)) rc = sweep_step(s, sw);
-    if (sw.keep_warm) {
-        if (rc) { I.resident = false; I.why_not = MI355SAT_COLD_FIRST; }
-        else if (searched) {
+    // 3. what the next solve() finds on the device (an error that leaves by exception: mi355sat_solve goes cold)
+    if (sw.keep_warm && rc) go_cold(s, MI355SAT_COLD_FIRST);
+    else if (sw.keep_warm) {
+        if (uploaded) I.resident = true;
+        if (searched) {
             I.base = sw.sts;    // (empty: interrupted before the first slice - the workers are as the template left them)
             I.base.resize(s.n_workers, MsState{});
             for (const MsState& st : sw.sts) if (st.status == MS_ST_UNSAT) I.refuted = true;
@@ -2434,10 +2509,7 @@ void sweep_repose(mi355sat& s, Sweep& sw, uint32_t inst, const std::vector<int32
     sw.base_src.erase(sw.base_src.begin() + b0, sw.base_src.begin() + b1);
     sw.base_src.insert(sw.base_src.begin() + b0, src.begin(), src.end());
     for (uint32_t i = inst + 1; i <= sw.n_instances; i++) sw.base_off[i] = sw.base_off[i] - (b1 - b0) + a_int.size();
-    sw.results[inst] = MI355SAT_INTERRUPTED;
-    sw.winner[inst] = -1;
-    sw.dropped[inst] = 0;
-    sw.core_flag[inst].assign(lits.size(), 0);
+    sw.pose(inst, lits.size());
 }
 
 // After the instances of a round are posed: every worker that has a slab moves to one of them (rebalance_workers ->
@@ -2453,12 +2525,6 @@ void sweep_retarget(mi355sat& s, Sweep& sw) {
     HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
 }
 
-inline int32_t device_literal(const mi355sat& s, int32_t d) {      // the walk of map_assumptions for one literal
-    int32_t l = to_internal(d);
-    while (s.subst[l >> 1] != 2 * (l >> 1)) l = s.subst[l >> 1] ^ (l & 1);
-    return 2 * (int32_t)s.perm[l >> 1] | (l & 1);
-}
-
 // What the models of SAT candidates say about the literals they did not assume: ms_core_model_kernel, one wave per
 // winner, on the stream after the slice and ahead of anything that rewrites a slab's assumptions (a SAT instance's winner
 // keeps its slab until sweep_retarget).  chunks[k] = the caller's literals winner k's candidate left out; falsified[k]
@@ -2466,7 +2532,6 @@ inline int32_t device_literal(const mi355sat& s, int32_t d) {      // the walk o
 int core_models(mi355sat& s, Sweep& sw, const std::vector<int32_t>& winners, const std::vector<std::vector<int32_t>>& chunks,
                 std::vector<std::vector<std::vector<uint32_t>>>& falsified, mi355sat_core_min_info& info) {
     const uint32_t n = (uint32_t)winners.size();
-    const uint32_t out_words = std::max<uint32_t>(1, (s.L.assump_cap + 31) / 32);
     std::vector<int32_t> lits, q;
     std::vector<uint64_t> off{0}, q_off64;
     std::vector<uint32_t> src;
@@ -2474,34 +2539,23 @@ int core_models(mi355sat& s, Sweep& sw, const std::vector<int32_t>& winners, con
     map_assumptions(s, s.perm, s.n_vars, lits, off, n, q, q_off64, src);
     std::vector<uint32_t> q_off(q_off64.begin(), q_off64.end());
     for (uint32_t k = 0; k < n; k++)
-        if (q_off[k + 1] - q_off[k] > out_words * 32u || (uint32_t)winners[k] >= s.n_alloc) throw HipErr{"core minimisation: list out of range"};
+        if (q_off[k + 1] - q_off[k] > 32u * bit_row_words(s) || (uint32_t)winners[k] >= s.n_alloc) throw HipErr{"core minimisation: list out of range"};
     sw.d_fw.upload(winners, s.stream);
     sw.d_qlits.upload(q.empty() ? std::vector<int32_t>{0} : q, s.stream);
     sw.d_qoff.upload(q_off, s.stream);
-    if (sw.d_fout.n < (size_t)n * out_words) sw.d_fout.alloc((size_t)n * out_words);
-    if (sw.d_fok.n < n) sw.d_fok.alloc(n);
-    hipLaunchKernelGGL(ms_core_model_kernel, dim3(n), dim3(MS_WAVE), 0, s.stream, s.L, (const char*)s.d_slabs.p, (const int32_t*)sw.d_fw.p,
-                       (const int32_t*)sw.d_qlits.p, (const uint32_t*)sw.d_qoff.p, sw.d_fout.p, out_words, sw.d_fok.p);
-    HIPCHK(hipGetLastError());
-    info.model_launches++;
-    std::vector<uint32_t> out((size_t)n * out_words);
-    std::vector<int32_t> ok(n);
-    HIPCHK(hipMemcpyAsync(out.data(), sw.d_fout.p, sizeof(uint32_t) * out.size(), hipMemcpyDeviceToHost, s.stream));
-    HIPCHK(hipMemcpyAsync(ok.data(), sw.d_fok.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s.stream));
-    HIPCHK(hipStreamSynchronize(s.stream));
     falsified.assign(n, {});
-    for (uint32_t k = 0; k < n; k++) {
-        if (!ok[k]) { set_error(&s, "device solver internal error (a SAT worker's slab is no model)"); return MI355SAT_ERR_STATE; }
-        const uint32_t b0 = q_off[k], nb = q_off[k + 1] - b0;
-        for (uint32_t i = 0; i < nb; i++) {
-            if (!((out[(size_t)k * out_words + i / 32] >> (i % 32)) & 1u)) continue;
-            std::vector<uint32_t> pos;
-            for (uint32_t p = src[b0 + i]; p < chunks[k].size(); p++)       // (src: the first position that maps to it)
-                if (device_literal(s, chunks[k][p]) == q[b0 + i]) pos.push_back(p);
-            falsified[k].push_back(pos);
-        }
-    }
-    return 0;
+    return read_bit_rows(s, sw, n, "device solver internal error (a SAT worker's slab is no model)", [&](uint32_t out_words) {
+        hipLaunchKernelGGL(ms_core_model_kernel, dim3(n), dim3(MS_WAVE), 0, s.stream, s.L, (const char*)s.d_slabs.p, (const int32_t*)sw.d_fw.p,
+                           (const int32_t*)sw.d_qlits.p, (const uint32_t*)sw.d_qoff.p, sw.d_fout.p, out_words, sw.d_fok.p);
+        info.model_launches++;
+    }, [&](uint32_t k, uint32_t i) {
+        const uint32_t b0 = q_off[k];
+        if (i >= q_off[k + 1] - b0) return;
+        std::vector<uint32_t> pos;
+        for (uint32_t p = src[b0 + i]; p < chunks[k].size(); p++)       // (src: the first position that maps to it)
+            if (device_literal(s, s.perm, chunks[k][p]) == q[b0 + i]) pos.push_back(p);
+        falsified[k].push_back(pos);
+    });
 }
 
 // The loop.  K: the working core (caller's literals, in the caller's order), crit[i]: K[i] is proved critical (formula
@@ -2622,46 +2676,32 @@ int minimize_search(mi355sat& s, std::vector<int32_t>& K, int64_t budget, mi355s
     return rc;
 }
 
-// core: the handle's core to minimise in place; minimal: its cached flag.  Returns 0 or a negative error.
-int minimize_core_impl(mi355sat* s, std::vector<int32_t>& core, bool& minimal, int64_t conflict_budget, mi355sat_core_min_info* out) {
+// core: the handle's core to minimise in place.  Returns 0 or a negative error.
+int minimize_core_impl(mi355sat* s, Core& core, int64_t conflict_budget, mi355sat_core_min_info* out) {
     mi355sat_core_min_info info{};
-    info.size_before = info.size_after = core.size();
+    info.size_before = info.size_after = core.lits.size();
     const double t0 = now_s();
     int rc = 0;
     if (s->interrupted.load()) consume_interrupt(*s);                 // stopped at once: the core as it is
-    else if (minimal || core.empty()) { info.minimal = 1; minimal = true; }
-    else if (core.size() == 1 && s->sat_clauses == s->offs.size()) { info.minimal = 1; minimal = true; }   // the formula alone has a model
+    else if (core.minimal || core.lits.empty()) { info.minimal = 1; core.minimal = true; }
+    else if (core.lits.size() == 1 && s->sat_clauses == s->offs.size()) { info.minimal = 1; core.minimal = true; }   // the formula alone has a model
     else {
-        s->inc.resident = false;                                      // "another search in between" for the warm mode
-        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
+        go_cold(*s, MI355SAT_COLD_OTHER_SEARCH);                      // "another search in between" for the warm mode
         const mi355sat_opts opts = s->opts;
-        const mi355sat_stats_t st0 = s->stats;                        // (what describes the caller's last solve stays: below)
+        const mi355sat_stats_t st0 = s->stats;
         std::string proof_path;
         proof_path.swap(s->proof_path);                               // the proof of the solve is closed: nothing is logged
         s->opts.cube_split = 0;                                       // candidates are whole instances, one core each
-        std::vector<int32_t> K = core;
-        try {
-            HIPCHK(hipSetDevice(s->device));
-            rc = minimize_search(*s, K, conflict_budget, info);
-        } catch (HipErr& he) {
-            s->err = he.msg;
-            rc = MI355SAT_ERR_HIP;
-        } catch (std::bad_alloc&) {
-            s->err = "out of host memory";
-            rc = MI355SAT_ERR_OOM;
-        }
+        std::vector<int32_t> K = core.lits;
+        rc = guarded(s, GUARD_TIMED, [&] { return minimize_search(*s, K, conflict_budget, info); });
         s->opts = opts;
         s->proof_path.swap(proof_path);
-        // the simplification counters and the fleet size are those of the caller's last solve / batch, not of this upload
-        s->stats.simp_units = st0.simp_units; s->stats.simp_equivalences = st0.simp_equivalences;
-        s->stats.simp_clauses_removed = st0.simp_clauses_removed; s->stats.simp_eliminated = st0.simp_eliminated;
-        s->stats.workers = st0.workers;
+        keep_last_solve_stats(s->stats, st0);                         // (not this upload's)
         if (!rc) {
-            core.swap(K);
-            minimal = info.minimal != 0;
-            info.size_after = core.size();
+            core.lits.swap(K);
+            core.minimal = info.minimal != 0;
+            info.size_after = core.lits.size();
         }
-        s->stats.solve_seconds += now_s() - t0;
     }
     info.seconds = now_s() - t0;
     if (out) *out = info;
@@ -2734,21 +2774,22 @@ mi355sat* mi355sat_new(const mi355sat_opts* opts) {
 
 void mi355sat_free(mi355sat* s) {
     if (!s) return;
+    // The order: the handle's device selected and its stream idle before anything goes; the sweep and the proof file are
+    // not the handle's members, so by hand; then `delete s`, whose members' destructors return every device buffer (the
+    // slabs: parked for the next handle) while that device is still the current one; the pinned flag, the events and the
+    // stream are plain handles the destructor does not know about, and the stream outlives the buffers that were used on it.
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     delete s->sweep;
     if (s->proof_file) fclose(s->proof_file);
-    s->d_cl_lits.release(); s->d_bin_lits.release();
-    s->d_tern_pairs.release(); s->d_tern_owner.release();
-    s->d_template.release(); s->d_slabs.release(); s->d_states.release(); s->d_any_done.release();
-    s->d_proof.release(); s->d_proof_len.release();
-    s->d_assump.release(); s->d_script.release(); s->d_assump_off.release(); s->d_script_off.release();
-    s->d_inc_lits.release(); s->d_inc_offs.release(); s->d_phase.release();
-    if (s->stop_flag) (void)hipHostFree(s->stop_flag);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    int32_t* const stop_flag = s->stop_flag;
+    const hipEvent_t ev0 = s->ev0, ev1 = s->ev1;
+    const hipStream_t stream = s->stream;
     delete s;
+    if (stop_flag) (void)hipHostFree(stop_flag);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 int mi355sat_reserve(mi355sat* s, uint64_t n_vars) {
@@ -2762,13 +2803,12 @@ static int add_clause_impl(mi355sat* s, const int32_t* l, uint64_t n) {
     for (uint64_t i = 0; i < n; i++) {
         int32_t d = l[i];
         if (d == 0 || d == INT32_MIN) { s->err = "literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
-        uint64_t v = (uint64_t)(d < 0 ? -(int64_t)d : d);
-        if (v > MS_MAX_VARS) { s->err = "variable index too large"; return MI355SAT_ERR_ARG; }
-        if (v > s->max_var) s->max_var = v;
+        if (var_of(d) > MS_MAX_VARS) { s->err = "variable index too large"; return MI355SAT_ERR_ARG; }
+        if (var_of(d) > s->max_var) s->max_var = var_of(d);
     }
     s->lits.insert(s->lits.end(), l, l + n);
     s->offs.push_back(s->lits.size());
-    s->core_valid = false;     // IPASIR: adding leaves the UNSAT state
+    s->core.valid = false;     // IPASIR: adding leaves the UNSAT state
     s->stats.n_clauses++;
     s->stats.max_var = s->max_var;
     s->stats.avg_clause_len = (double)s->lits.size() / (double)s->stats.n_clauses;
@@ -2777,24 +2817,24 @@ static int add_clause_impl(mi355sat* s, const int32_t* l, uint64_t n) {
 
 int mi355sat_add_cnf(mi355sat* s, const int32_t* lits, const uint64_t* offsets, uint64_t n_clauses) {
     if (!s || (n_clauses && (!offsets || (!lits && offsets[n_clauses] > offsets[0])))) return MI355SAT_ERR_ARG;
-    try {
+    return guarded(s, GUARD_HOST, [&] {
         for (uint64_t c = 0; c < n_clauses; c++) {
             if (offsets[c + 1] < offsets[c]) { s->err = "offsets not monotone"; return MI355SAT_ERR_ARG; }
             int rc = add_clause_impl(s, lits + offsets[c], offsets[c + 1] - offsets[c]);
             if (rc) return rc;
         }
-    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
-    return 0;
+        return 0;
+    });
 }
 
 int mi355sat_add(mi355sat* s, int32_t lit_or_0) {
     if (!s) return MI355SAT_ERR_ARG;
-    try {
+    return guarded(s, GUARD_HOST, [&] {
         if (lit_or_0 != 0) { s->pending.push_back(lit_or_0); return 0; }
         int rc = add_clause_impl(s, s->pending.data(), s->pending.size());
         s->pending.clear();
         return rc;
-    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 void mi355sat_interrupt(mi355sat* s) {
@@ -2805,61 +2845,62 @@ void mi355sat_interrupt(mi355sat* s) {
 
 int mi355sat_assume(mi355sat* s, int32_t lit) {
     if (!s) return MI355SAT_ERR_ARG;
-    const uint64_t v = (uint64_t)(lit < 0 ? -(int64_t)lit : lit);
+    const uint64_t v = var_of(lit);
     if (lit == 0 || v > MS_MAX_VARS) { s->err = "assumption literal out of range"; return MI355SAT_ERR_ARG; }
-    try {
-        s->assumps.push_back(lit);
-    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    if (int rc = guarded(s, GUARD_HOST, [&] { s->assumps.push_back(lit); return 0; })) return rc;
     if (v > s->max_var) { s->max_var = v; s->stats.max_var = v; }   // as mi355sat_reserve
-    s->core_valid = false;
+    s->core.valid = false;
     return 0;
 }
 
 int mi355sat_failed(mi355sat* s, int32_t lit) {
     if (!s) return MI355SAT_ERR_ARG;
-    if (!s->core_valid) { s->err = "no failed assumptions: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
-    return std::find(s->core.begin(), s->core.end(), lit) != s->core.end() ? 1 : 0;
+    if (!s->core.valid) { s->err = "no failed assumptions: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    return std::find(s->core.lits.begin(), s->core.lits.end(), lit) != s->core.lits.end() ? 1 : 0;
 }
 
-static int copy_core(mi355sat* s, const std::vector<int32_t>& core, int32_t* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = core.size();
+static int copy_core(mi355sat* s, const Core& core, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = core.lits.size();
     if (!out) return 0;
-    if (cap < core.size()) { s->err = "core buffer too small"; return MI355SAT_ERR_ARG; }
-    std::copy(core.begin(), core.end(), out);
+    if (cap < core.lits.size()) { s->err = "core buffer too small"; return MI355SAT_ERR_ARG; }
+    std::copy(core.lits.begin(), core.lits.end(), out);
     return 0;
+}
+
+// The core of instance `instance` of the last solve_batch() into *core, or why there is none (`what`: how the message
+// begins): MI355SAT_ERR_ARG for an index beyond that batch, MI355SAT_ERR_STATE where there was no batch or the instance
+// was not UNSAT - or the core is not to be touched now (blocked).
+static int find_batch_core(mi355sat* s, uint64_t instance, const char* what, Core** core, bool blocked = false) {
+    const size_t n = s->batch_cores.size();
+    if (instance < n && s->batch_cores[instance].valid && !blocked) { *core = &s->batch_cores[instance]; return 0; }
+    s->err = std::string(what) + ": instance out of range or not UNSAT in the last solve_batch()";
+    return instance >= n && n ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
 }
 
 int mi355sat_core(mi355sat* s, int32_t* out, uint64_t cap, uint64_t* n) {
     if (!s) return MI355SAT_ERR_ARG;
-    if (!s->core_valid) { s->err = "no core: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    if (!s->core.valid) { s->err = "no core: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
     return copy_core(s, s->core, out, cap, n);
 }
 
 int mi355sat_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n) {
     if (!s) return MI355SAT_ERR_ARG;
-    if (instance >= s->batch_core_valid.size() || !s->batch_core_valid[instance]) {
-        s->err = "no core: instance out of range or not UNSAT in the last solve_batch()";
-        return instance >= s->batch_core_valid.size() && !s->batch_core_valid.empty() ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
-    }
-    return copy_core(s, s->batch_cores[instance], out, cap, n);
+    Core* core = nullptr;
+    if (int rc = find_batch_core(s, instance, "no core", &core)) return rc;
+    return copy_core(s, *core, out, cap, n);
 }
 
 int mi355sat_minimize_core(mi355sat* s, int64_t conflict_budget, mi355sat_core_min_info* out) {
     if (!s || conflict_budget < 0) return MI355SAT_ERR_ARG;
-    if (!s->core_valid || s->sweep) { s->err = "no core to minimise: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
-    return minimize_core_impl(s, s->core, s->core_minimal, conflict_budget, out);
+    if (!s->core.valid || s->sweep) { s->err = "no core to minimise: the last solve() did not return UNSAT"; return MI355SAT_ERR_STATE; }
+    return minimize_core_impl(s, s->core, conflict_budget, out);
 }
 
 int mi355sat_minimize_core_of(mi355sat* s, uint64_t instance, int64_t conflict_budget, mi355sat_core_min_info* out) {
     if (!s || conflict_budget < 0) return MI355SAT_ERR_ARG;
-    if (instance >= s->batch_core_valid.size() || !s->batch_core_valid[instance] || s->sweep) {
-        s->err = "no core to minimise: instance out of range or not UNSAT in the last solve_batch()";
-        return instance >= s->batch_core_valid.size() && !s->batch_core_valid.empty() ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
-    }
-    bool minimal = s->batch_core_minimal[instance] != 0;
-    const int rc = minimize_core_impl(s, s->batch_cores[instance], minimal, conflict_budget, out);
-    s->batch_core_minimal[instance] = minimal ? 1 : 0;
-    return rc;
+    Core* core = nullptr;
+    if (int rc = find_batch_core(s, instance, "no core to minimise", &core, /*blocked=*/s->sweep != nullptr)) return rc;
+    return minimize_core_impl(s, *core, conflict_budget, out);
 }
 
 int mi355sat_debug_core_min_round(mi355sat* s, uint32_t max_candidates) {
@@ -2885,11 +2926,9 @@ static int set_hint(mi355sat* s, uint64_t v, int8_t h) {      // v 1-based
 
 int mi355sat_phase(mi355sat* s, int32_t lit) {
     if (!s) return MI355SAT_ERR_ARG;
-    const uint64_t v = (uint64_t)(lit < 0 ? -(int64_t)lit : lit);
+    const uint64_t v = var_of(lit);
     if (lit == 0 || v > MS_MAX_VARS) { s->err = "phase literal out of range"; return MI355SAT_ERR_ARG; }
-    try {
-        set_hint(s, v, lit > 0 ? 1 : -1);
-    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    if (int rc = guarded(s, GUARD_HOST, [&] { return set_hint(s, v, lit > 0 ? 1 : -1); })) return rc;
     if (v > s->max_var) { s->max_var = v; s->stats.max_var = v; }   // as mi355sat_reserve
     return 0;
 }
@@ -2903,15 +2942,15 @@ int mi355sat_unphase(mi355sat* s, int32_t var) {
 int mi355sat_set_phases(mi355sat* s, const int8_t* phases, uint64_t n_vars) {
     if (!s || (n_vars && !phases)) return MI355SAT_ERR_ARG;
     if (n_vars > MS_MAX_VARS) { s->err = "variable index too large"; return MI355SAT_ERR_ARG; }
-    try {
+    return guarded(s, GUARD_HOST, [&] {
         uint64_t top = 0;
         for (uint64_t v = 1; v <= n_vars; v++) {
             set_hint(s, v, phases[v - 1] > 0 ? 1 : (phases[v - 1] < 0 ? -1 : 0));
             if (phases[v - 1]) top = v;
         }
         if (top > s->max_var) { s->max_var = top; s->stats.max_var = top; }
-    } catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
-    return 0;
+        return 0;
+    });
 }
 
 int mi355sat_debug_phases(const mi355sat* s, mi355sat_phase_info* out) {
@@ -2929,7 +2968,7 @@ int mi355sat_set_proof_path(mi355sat* s, const char* path) {
 int mi355sat_set_incremental(mi355sat* s, int on) {
     if (!s) return MI355SAT_ERR_ARG;
     s->inc.on = on != 0;
-    if (!s->inc.on) { s->inc.resident = false; s->inc.why_not = MI355SAT_COLD_FIRST; }
+    if (!s->inc.on) go_cold(*s, MI355SAT_COLD_FIRST);
     return 0;
 }
 
@@ -2949,8 +2988,7 @@ int mi355sat_debug_heuristics(const mi355sat* s, mi355sat_heuristics_info* out) 
 int mi355sat_debug_set_schedule(mi355sat* s, uint32_t first_vivify, uint32_t vivify_every, uint32_t rephase_every) {
     if (!s || vivify_every > 0xffffu || rephase_every > 0xffffu) return MI355SAT_ERR_ARG;
     s->first_vivify = first_vivify; s->vivify_every = vivify_every; s->rephase_every = rephase_every;
-    s->inc.resident = false;      // next_vivify / next_rephase are part of a worker's state: the next solve starts cold
-    s->inc.why_not = MI355SAT_COLD_FIRST;
+    go_cold(*s, MI355SAT_COLD_FIRST);      // next_vivify / next_rephase are part of a worker's state
     return 0;
 }
 
@@ -2958,92 +2996,57 @@ int mi355sat_solve(mi355sat* s) {
     if (!s) return MI355SAT_ERR_ARG;
     std::vector<int32_t> assump;
     assump.swap(s->assumps);     // IPASIR: the assumptions hold for this solve only, whatever it returns
-    s->core.clear();
-    s->core_valid = false;
-    s->core_minimal = false;
+    s->core = Core{};
     if (!s->pending.empty()) { s->err = "solve() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
-    const double t0 = now_s();
-    int result;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    const int rc = guarded(s, GUARD_TIMED, [&] {
         std::vector<uint64_t> aoff{0, (uint64_t)assump.size()};
         std::vector<int32_t> results, winner;
         std::vector<std::vector<int32_t>> cores;
-        int rc = run_search(*s, assump, aoff, 1, results, winner, true, &cores, /*plain_solve=*/true);
-        if (rc) { proof_close(*s, false); s->stats.solve_seconds += now_s() - t0; return rc; }   // (a truncated proof file is closed, not leaked)
-        result = results[0];
-        if (result == MI355SAT_UNSAT) { s->core = cores[0]; s->core_valid = true; }
-        proof_close(*s, result == MI355SAT_UNSAT, s->core);
+        if (int err = run_search(*s, assump, aoff, 1, results, winner, true, &cores, /*plain_solve=*/true)) return err;
+        const int result = results[0];
+        if (result == MI355SAT_UNSAT) { s->core.lits = cores[0]; s->core.valid = true; }
+        proof_close(*s, result == MI355SAT_UNSAT, s->core.lits);
         s->model.clear();
         if (result == MI355SAT_SAT) fetch_model(*s, (uint32_t)winner[0], s->model, s->max_var);
-    } catch (HipErr& he) {
+        tally_answer(*s, result);
+        return result;
+    });
+    if (rc < 0) {      // a failed solve: its truncated proof file is closed, not leaked, and the next solve() starts cold
         proof_close(*s, false);
-        s->inc.resident = false;
-        s->inc.why_not = MI355SAT_COLD_FIRST;
-        s->err = he.msg;
-        s->stats.solve_seconds += now_s() - t0;
-        return MI355SAT_ERR_HIP;
-    } catch (std::bad_alloc&) {
-        s->err = "out of host memory";
-        return MI355SAT_ERR_OOM;
+        go_cold(*s, MI355SAT_COLD_FIRST);
     }
-    if (result == MI355SAT_SAT) { s->stats.n_sat++; s->sat_clauses = s->offs.size(); }
-    else if (result == MI355SAT_UNSAT) s->stats.n_unsat++;
-    else s->stats.n_terminated++;
-    s->stats.solve_seconds += now_s() - t0;
-    return result;
+    return rc;
 }
 
 int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* assump_offsets, uint64_t n_instances,
                          int32_t* results_out, int stop_at_first) {
     if (!s || !assump_offsets || !results_out || n_instances == 0) return MI355SAT_ERR_ARG;
-    const double t0 = now_s();
-    try {
-        HIPCHK(hipSetDevice(s->device));
-        std::vector<uint64_t> aoff(assump_offsets, assump_offsets + n_instances + 1);
-        for (auto& o : aoff) o -= assump_offsets[0];
-        std::vector<int32_t> assump;
-        if (aoff.back()) assump.assign(assumps + assump_offsets[0], assumps + assump_offsets[n_instances]);
-        std::vector<int32_t> results, winner;
+    return guarded(s, GUARD_TIMED, [&] {
+        std::vector<int32_t> assump, results, winner;
+        std::vector<uint64_t> aoff;
+        copy_lists(assumps, assump_offsets, n_instances, assump, aoff);
         s->batch_cores.clear();
-        s->batch_core_valid.clear();
-        s->batch_core_minimal.clear();
         std::vector<std::vector<int32_t>> cores;
-        int rc = run_search(*s, assump, aoff, (uint32_t)n_instances, results, winner, stop_at_first != 0, &cores);
-        if (rc) { s->stats.solve_seconds += now_s() - t0; return rc; }
+        if (int err = run_search(*s, assump, aoff, (uint32_t)n_instances, results, winner, stop_at_first != 0, &cores)) return err;
         s->batch_models.assign(n_instances, {});
-        s->batch_cores.swap(cores);
-        s->batch_core_valid.assign(n_instances, 0);
-        s->batch_core_minimal.assign(n_instances, 0);
+        s->batch_cores.assign(n_instances, Core{});
         for (uint64_t i = 0; i < n_instances; i++) {
             results_out[i] = results[i];
-            s->batch_core_valid[i] = results[i] == MI355SAT_UNSAT;
+            s->batch_cores[i].lits.swap(cores[i]);
+            s->batch_cores[i].valid = results[i] == MI355SAT_UNSAT;
             if (results[i] == MI355SAT_SAT && winner[i] >= 0) fetch_model(*s, (uint32_t)winner[i], s->batch_models[i], s->max_var);
-            if (results[i] == MI355SAT_SAT) { s->stats.n_sat++; s->sat_clauses = s->offs.size(); }
-            else if (results[i] == MI355SAT_UNSAT) s->stats.n_unsat++;
-            else s->stats.n_terminated++;
+            tally_answer(*s, results[i]);
         }
-    } catch (HipErr& he) {
-        s->err = he.msg;
-        s->stats.solve_seconds += now_s() - t0;
-        return MI355SAT_ERR_HIP;
-    } catch (std::bad_alloc&) {
-        s->err = "out of host memory";
-        return MI355SAT_ERR_OOM;
-    }
-    s->stats.solve_seconds += now_s() - t0;
-    return 0;
+        return 0;
+    });
 }
 
 int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64_t* decision_offsets,
                              uint64_t n_instances, int8_t* out_values, uint64_t n_vars, int32_t* out_conflict,
                              int32_t* out_trail_len, int32_t repeat) {
     if (!s || !decision_offsets || n_instances == 0) return MI355SAT_ERR_ARG;
-    const double t0 = now_s();
-    try {
-        HIPCHK(hipSetDevice(s->device));
-        s->inc.resident = false;     // (the slabs become this batch's)
-        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
+    return guarded(s, GUARD_TIMED, [&] {
+        go_cold(*s, MI355SAT_COLD_OTHER_SEARCH);     // (the slabs become this batch's)
         s->ph.on_device = false;     // scripted BCP decides nothing: no phase hints
         Prepared P;
         prepare(*s, /*simplify=*/false, P);
@@ -3055,15 +3058,14 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
             if (out_values) memset(out_values, 0, n_instances * n_vars);
             return 0;
         }
-        std::vector<uint64_t> soff(decision_offsets, decision_offsets + n_instances + 1);
-        for (auto& o : soff) o -= decision_offsets[0];
-        std::vector<int32_t> script(soff.back());
+        std::vector<int32_t> script;
+        std::vector<uint64_t> soff;
+        copy_lists(decisions, decision_offsets, n_instances, script, soff);
         uint32_t max_script = 0;
         for (uint64_t i = 0; i < n_instances; i++) max_script = std::max<uint32_t>(max_script, (uint32_t)(soff[i + 1] - soff[i]));
-        for (uint64_t k = 0; k < soff.back(); k++) {
-            int32_t d = decisions[decision_offsets[0] + k];
-            if (d == 0 || (uint64_t)(d < 0 ? -(int64_t)d : d) > P.n_vars) throw HipErr{"decision literal out of range"};
-            script[k] = to_device(P.perm, d);
+        for (int32_t& d : script) {
+            if (d == 0 || var_of(d) > P.n_vars) throw HipErr{"decision literal out of range"};
+            d = to_device(P.perm, d);
         }
         upload_formula(*s, P, 0, max_script, (uint32_t)n_instances);
         if (s->n_workers < n_instances) throw HipErr{"not enough device memory for the batch"};
@@ -3080,19 +3082,7 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
             if (out_conflict) out_conflict[i] = sts[i].status == MS_ST_UNSAT ? 1 : 0;
             if (out_trail_len) out_trail_len[i] = sts[i].trail_n;
         }
-        // counters of the last repeat only, scaled
-        {
-            std::vector<MsState> one = sts;
-            accumulate_stats(*s, one);
-            if (repeat > 1) {
-                mi355sat_stats_t& o = s->stats;
-                uint64_t props = 0, nw = 0, ncl = 0, nm = 0, ne = 0;
-                for (auto& st : sts) { props += st.propagations; nw += st.n_watch; ncl += st.n_cl_lit; nm += st.n_move; ne += st.n_enq; }
-                uint64_t k = (uint64_t)(repeat - 1);
-                o.propagations += props * k; o.n_deq += props * k; o.n_watch += nw * k; o.n_cl_lit += ncl * k;
-                o.n_move += nm * k; o.n_enq += ne * k;
-            }
-        }
+        accumulate_stats(*s, sts, (uint64_t)repeat);     // counters of the last repeat only, scaled
         if (out_values) {
             const size_t nw = P.n_vars;
             std::vector<uint8_t> raw(n_instances * nw + 1);
@@ -3105,64 +3095,47 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
                     out_values[i * n_vars + v] = x == MS_ASG_TRUE ? 1 : (x == MS_ASG_FALSE ? -1 : 0);
                 }
         }
-    } catch (HipErr& he) {
-        s->err = he.msg;
-        s->stats.solve_seconds += now_s() - t0;
-        return MI355SAT_ERR_HIP;
-    } catch (std::bad_alloc&) {
-        s->err = "out of host memory";
-        return MI355SAT_ERR_OOM;
-    }
-    s->stats.solve_seconds += now_s() - t0;
-    return 0;
+        return 0;
+    });
 }
 
 int mi355sat_sweep_begin(mi355sat* s, const int32_t* assumps, const uint64_t* assump_offsets, uint64_t n_instances) {
     if (!s || !assump_offsets || n_instances == 0) return MI355SAT_ERR_ARG;
-    try {
-        HIPCHK(hipSetDevice(s->device));
-        std::vector<uint64_t> aoff(assump_offsets, assump_offsets + n_instances + 1);
-        for (auto& o : aoff) o -= assump_offsets[0];
+    return guarded(s, GUARD_DEVICE, [&] {
         std::vector<int32_t> assump;
-        if (aoff.back()) assump.assign(assumps + assump_offsets[0], assumps + assump_offsets[n_instances]);
+        std::vector<uint64_t> aoff;
+        copy_lists(assumps, assump_offsets, n_instances, assump, aoff);
         delete s->sweep;
         s->sweep = new SweepHolder;
         s->sweep->base = s->stats;
-        s->inc.resident = false;
-        s->inc.why_not = MI355SAT_COLD_OTHER_SEARCH;
+        go_cold(*s, MI355SAT_COLD_OTHER_SEARCH);
         return sweep_begin(*s, s->sweep->sw, assump, aoff, (uint32_t)n_instances, false);
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_sweep_step(mi355sat* s, int32_t* results_out, uint64_t* n_decided) {
     if (!s || !s->sweep) return MI355SAT_ERR_STATE;
-    const double t0 = now_s();
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_TIMED, [&] {
         Sweep& sw = s->sweep->sw;
         int rc = sweep_step(*s, sw);
         if (results_out) for (uint32_t i = 0; i < sw.n_instances; i++) results_out[i] = sw.results[i];
         if (n_decided) *n_decided = sw.decided;
-        // running totals so that stats() is meaningful between steps
-        mi355sat_stats_t keep = s->stats;
+        // running totals so that stats() is meaningful between steps: what they were when the sweep began, this sweep's
+        // times, and the workers' counters as they stand
+        const mi355sat_stats_t keep = s->stats;
         s->stats = s->sweep->base;
         s->stats.kernel_seconds = keep.kernel_seconds;
         s->stats.kernel_launches = keep.kernel_launches;
-        s->stats.workers = keep.workers;
-        s->stats.simp_units = keep.simp_units; s->stats.simp_equivalences = keep.simp_equivalences;
-        s->stats.simp_clauses_removed = keep.simp_clauses_removed; s->stats.simp_eliminated = keep.simp_eliminated;
-        s->stats.solve_seconds = keep.solve_seconds + (now_s() - t0);
+        s->stats.solve_seconds = keep.solve_seconds;
+        keep_last_solve_stats(s->stats, keep);
         accumulate_stats(*s, sw.sts);
         return rc;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n) {
     if (!s || !s->sweep || (n && !instances)) return MI355SAT_ERR_STATE;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         bool any = false;
         for (uint64_t j = 0; j < n; j++) {
@@ -3177,8 +3150,7 @@ int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n) {
             rebalance_workers(*s, sw);
         }
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_sweep_set_weights(mi355sat* s, const double* weights, uint64_t n) {
@@ -3193,8 +3165,7 @@ int mi355sat_sweep_set_weights(mi355sat* s, const double* weights, uint64_t n) {
 
 int mi355sat_sweep_reopen(mi355sat* s, const uint64_t* instances, uint64_t n) {
     if (!s || !s->sweep || (n && !instances)) return MI355SAT_ERR_STATE;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         bool any = false;
         for (uint64_t j = 0; j < n; j++) {
@@ -3210,14 +3181,12 @@ int mi355sat_sweep_reopen(mi355sat* s, const uint64_t* instances, uint64_t n) {
             rebalance_workers(*s, sw);   // parked workers and those of decided / withdrawn instances take them up
         }
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_sweep_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_t n_vars) {
     if (!s || !s->sweep || !out) return MI355SAT_ERR_STATE;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         if (instance >= sw.n_instances || sw.results[instance] != MI355SAT_SAT || sw.winner[instance] < 0) {
             s->err = "no model for that instance";
@@ -3227,13 +3196,12 @@ int mi355sat_sweep_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_
         fetch_model(*s, (uint32_t)sw.winner[instance], m, s->max_var);
         for (uint64_t v = 0; v < n_vars; v++) out[v] = v < m.size() ? m[v] : 0;
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_sweep_end(mi355sat* s) {
     if (!s || !s->sweep) return MI355SAT_ERR_STATE;
-    try {
+    return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         s->batch_models.assign(sw.n_instances, {});
         for (uint32_t i = 0; i < sw.n_instances; i++)
@@ -3243,12 +3211,12 @@ int mi355sat_sweep_end(mi355sat* s) {
         delete s->sweep;
         s->sweep = nullptr;
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
+    });
 }
 
 int32_t mi355sat_val(mi355sat* s, int32_t lit) {
     if (!s || lit == 0) return 0;
-    uint64_t v = (uint64_t)(lit < 0 ? -(int64_t)lit : lit);
+    const uint64_t v = var_of(lit);
     if (v > s->model.size()) return 0;
     int8_t m = s->model[v - 1];
     if (m == 0) return 0;
@@ -3278,8 +3246,7 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
     if (!s || !n_records) return MI355SAT_ERR_ARG;
     *n_records = 0;
     if (!s->share_slots || !s->d_share_pool.p) return 0;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         HIPCHK(hipStreamSynchronize(s->stream));
         unsigned long long n = 0;
         HIPCHK(hipMemcpy(&n, s->d_share_n.p, sizeof n, hipMemcpyDeviceToHost));
@@ -3304,8 +3271,7 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
             (*n_records)++;
         }
         return w <= cap_words || !out ? 0 : MI355SAT_ERR_ARG;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_debug_keep_simplified(mi355sat* s, int on) {
@@ -3352,8 +3318,7 @@ int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_
     if (!s || !n_words || !n_records) return MI355SAT_ERR_ARG;
     *n_words = 0; *n_records = 0;
     if (!s->share_slots || !s->d_share_pool.p || !s->sweep) return 0;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         HIPCHK(hipStreamSynchronize(s->stream));
         unsigned long long n = 0;
         HIPCHK(hipMemcpy(&n, s->d_share_n.p, sizeof n, hipMemcpyDeviceToHost));
@@ -3391,16 +3356,14 @@ int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_
         if (out) s->share_export_pos = consumed;     // (out == NULL only sizes the buffer)
         *n_words = w;
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words, uint64_t* n_records) {
     if (!s || (!clauses && n_words)) return MI355SAT_ERR_ARG;
     if (n_records) *n_records = 0;
     if (!n_words || !s->share_slots || !s->d_share_pool.p || !s->sweep) return 0;
-    try {
-        HIPCHK(hipSetDevice(s->device));
+    return guarded(s, GUARD_DEVICE, [&] {
         std::vector<uint8_t> gone(s->n_vars, 0);       // variables this handle's simplification resolved away
         for (const MsElim& e : s->elims) if ((uint32_t)(e.x >> 1) < gone.size()) gone[e.x >> 1] = 1;
         std::vector<int32_t> recs;
@@ -3412,12 +3375,10 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
             bool ok = lbd >= 1;
             while (i < n_words && clauses[i] != 0) {
                 const int32_t d = clauses[i++];
-                const uint64_t v = (uint64_t)(d < 0 ? -(int64_t)d : d);
-                if (v == 0 || v > s->n_vars || sz >= MS_SHARE_MAXLEN) { ok = false; continue; }
-                int32_t l = to_internal(d);
-                while ((size_t)(l >> 1) < s->subst.size() && s->subst[l >> 1] != 2 * (l >> 1)) l = s->subst[l >> 1] ^ (l & 1);
-                if (gone[l >> 1]) { ok = false; continue; }
-                rec[1 + sz++] = 2 * (int32_t)s->perm[l >> 1] | (l & 1);
+                if (var_of(d) > s->n_vars || sz >= MS_SHARE_MAXLEN) { ok = false; continue; }
+                const int32_t l = device_literal(*s, s->perm, d, &gone);     // (bounded by subst.size() there)
+                if (l < 0) { ok = false; continue; }
+                rec[1 + sz++] = l;
             }
             if (i >= n_words) { s->err = "share_import: clause without terminator"; return MI355SAT_ERR_ARG; }
             i++;   // the terminator
@@ -3442,8 +3403,7 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
         HIPCHK(hipMemcpy(s->d_share_n.p, &n, sizeof n, hipMemcpyHostToDevice));
         if (n_records) *n_records = n_new;
         return 0;
-    } catch (HipErr& he) { s->err = he.msg; return MI355SAT_ERR_HIP; }
-    catch (std::bad_alloc&) { s->err = "out of host memory"; return MI355SAT_ERR_OOM; }
+    });
 }
 
 int mi355sat_stats(const mi355sat* s, mi355sat_stats_t* out) {
