@@ -503,6 +503,52 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
  * worker may hold a copy of (exchanged or imported ones).  Must be called before solve(); path NULL disables. */
 int mi355sat_set_proof_path(mi355sat* s, const char* path);
 
+/* Check a DRUP proof on the device: a certificate for an UNSAT answer (ms_rup_kernel).
+ * Semantics: forward RUP with deletions ignored.  Lemma i must follow by unit propagation from the handle's clauses plus
+ * the lemmas before i; `target` - the clause the proof must derive, n_target = 0: the empty clause; for a solve under
+ * assumptions the negated core, which is the last line of the file mi355sat_set_proof_path writes - is checked as the last
+ * lemma, number n_lemmas.  Deletion lines are parsed, counted and ignored: every clause in the database is an original or
+ * a checked lemma and unit propagation is monotone, so this is sound, every valid DRUP proof passes, and the verdict is a
+ * function of formula, proof and target alone - not of `segments`, the worker count or the build.  A lemma that holds a
+ * literal and its negation counts as RUP.  Once formula + lemmas are refuted by propagation alone (refuted_at) every later
+ * lemma is RUP trivially.
+ * Trusted base: the handle's clauses as the caller added them - no simplification, the caller's variable order; the
+ * handle need not have solved anything (new, add_cnf, check_proof is a valid sequence).
+ * How: the lemma list (target included) is cut into `segments` contiguous parts (0 = the default: as many as the handle
+ * would use workers, at most n_lemmas + 1, fewer if device memory does not hold that many slabs); one wavefront per part
+ * attaches the lemmas before its part unchecked and checks its own.  Each worker holds a private copy of the lemmas
+ * up to the end of its part.
+ * proof: flat int32, lemmas 0-terminated, a deletion line = INT32_MIN, then the clause, then 0 (what the Python
+ * dimacs.read_drup returns).  A literal whose variable is above the handle's highest (mi355sat_reserve raises that), or an
+ * INT32_MIN inside a clause, is MI355SAT_ERR_ARG, found on the host before anything is uploaded.
+ * Returns 0 when the check ran to its end: out->valid is the verdict.  An interrupted check returns
+ * MI355SAT_INTERRUPTED (which is 0 as well) with out->valid = -1: no verdict; the call consumes the interrupt, and one
+ * that arrived before the call stops it before the first launch, as for a solve.  During a mi355sat_sweep_*:
+ * MI355SAT_ERR_STATE.  The call takes the device over as solve_batch does (with the incremental mode on, the next
+ * solve() starts cold: MI355SAT_COLD_OTHER_SEARCH); assumptions, failed / core and the phase hints are untouched;
+ * n_sat / n_unsat / n_terminated do not count it; solve_seconds, kernel_seconds and kernel_launches accumulate. */
+typedef struct mi355sat_proof_info {
+    int32_t  valid;              /* 1: every lemma is RUP in order and the target is RUP at the end; 0: not; -1: interrupted */
+    int32_t  pad;
+    uint64_t n_lemmas;           /* lemma lines (deletion lines not counted); the target is lemma number n_lemmas */
+    uint64_t n_deletions_ignored;
+    uint64_t first_failed;       /* smallest lemma index (0-based, target = n_lemmas) that is not RUP; UINT64_MAX if none */
+    uint64_t refuted_at;         /* smallest lemma index at which formula + lemmas before it are refuted by unit propagation alone; UINT64_MAX if never */
+    uint64_t segments, workers;  /* how the proof was cut, and how many wavefronts checked it */
+    uint64_t lemmas_checked, lemmas_attached;   /* summed over workers (attached counts the unchecked prefixes) */
+    uint64_t propagations;
+    uint64_t launches;
+    double   seconds, kernel_seconds;
+} mi355sat_proof_info;
+int mi355sat_check_proof(mi355sat* s, const int32_t* proof, uint64_t n_words,
+                         const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info* out);
+/* The same for a DRUP text file as mi355sat_set_proof_path writes it ("d ..." = a deletion line). */
+int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target,
+                              uint32_t segments, mi355sat_proof_info* out);
+/* Test hook: at most this many lemmas (checked or attached) per worker per launch, and no time bound; 0 = the default
+ * (launches of about 20 ms). */
+int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch);
+
 #ifdef __cplusplus
 }
 #endif

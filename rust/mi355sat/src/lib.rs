@@ -48,6 +48,22 @@ pub struct CoreMinInfo {
     pub critical_by_model: u64, pub model_launches: u64, pub conflicts: u64, pub seconds: f64,
 }
 
+/// Mirror of `mi355sat_proof_info`: what `check_proof` found.
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct ProofInfo {
+    /// 1: every lemma is RUP in order and the target is RUP at the end; 0: not; -1: the check was interrupted
+    pub valid: i32,
+    pub pad: i32,
+    pub n_lemmas: u64, pub n_deletions_ignored: u64,
+    /// smallest lemma index that is not RUP (the target is lemma number `n_lemmas`); `u64::MAX` if none
+    pub first_failed: u64,
+    /// smallest lemma index at which formula + lemmas before it are refuted by unit propagation alone; `u64::MAX` if never
+    pub refuted_at: u64,
+    pub segments: u64, pub workers: u64, pub lemmas_checked: u64, pub lemmas_attached: u64, pub propagations: u64,
+    pub launches: u64, pub seconds: f64, pub kernel_seconds: f64,
+}
+
 extern "C" {
     fn mi355sat_new(opts: *const Opts) -> *mut c_void;
     fn mi355sat_free(s: *mut c_void);
@@ -61,6 +77,8 @@ extern "C" {
     fn mi355sat_assume(s: *mut c_void, lit: i32) -> c_int;
     fn mi355sat_core(s: *mut c_void, out: *mut i32, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_minimize_core(s: *mut c_void, conflict_budget: i64, out: *mut CoreMinInfo) -> c_int;
+    fn mi355sat_check_proof(s: *mut c_void, proof: *const i32, n_words: u64, target: *const i32, n_target: u64, segments: u32,
+                            out: *mut ProofInfo) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
     fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
@@ -128,6 +146,19 @@ impl Mi355Sat {
         let mut info = CoreMinInfo::default();
         let b = budget.map_or(0, |b| b.clamp(1, i64::MAX as u64) as i64);
         if unsafe { mi355sat_minimize_core(self.h, b, &mut info) } < 0 { return Err(self.err()); }
+        Ok(info)
+    }
+    /// Certificate check (`mi355sat_check_proof`): forward RUP, deletion lines ignored, of a DRUP proof - flat words, lemmas
+    /// 0-terminated, a deletion line = `i32::MIN`, the clause, 0 - against this handle's clauses as they were added.
+    /// `target`: the clause the proof must derive (empty: the empty clause; after `solve_assumps`, the negated core).
+    /// `segments`: parts the lemma list is cut into, one wavefront each (0: the default); the verdict does not depend on
+    /// it.  `valid == -1`: an interrupt ended the check.  The next warm solve starts cold.
+    pub fn check_proof(&mut self, proof: &[i32], target: &[i32], segments: u32) -> anyhow::Result<ProofInfo> {
+        let mut info = ProofInfo::default();
+        let rc = unsafe {
+            mi355sat_check_proof(self.h, proof.as_ptr(), proof.len() as u64, target.as_ptr(), target.len() as u64, segments, &mut info)
+        };
+        if rc < 0 { return Err(self.err()); }
         Ok(info)
     }
     fn err(&self) -> anyhow::Error {

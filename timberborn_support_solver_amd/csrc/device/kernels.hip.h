@@ -350,6 +350,7 @@ DEV MsClauseHdr clause_hdr_of(const Wk& w, const MsShared& sh, const MsLayout& L
 // trip instead of two dependent ones.
 // Append (cref, blocker) to the list of literal t (uniform call, rare path:
 // learnt clause attach and overflow repair).  Grows the list from the bump pool.
+DEV uint32_t list_grown_cap(uint32_t cap) { return cap < 4 ? 8 : cap * 2; }   // the slot a full list moves to
 DEV bool list_push_uniform(Wk& w, const MsShared& sh, const MsLayout& L, int t, int cref, int blocker, uint32_t start, uint32_t size) {
     Gp<MsWatchHdr> whdr = WKA(MsWatchHdr, whdr);
     Gp<int4> pool = WKA(int4, pool);
@@ -358,7 +359,7 @@ DEV bool list_push_uniform(Wk& w, const MsShared& sh, const MsLayout& L, int t, 
     if (s > cap) s = cap;  // overshoot left by failed atomic pushes
     uint32_t base = (uint32_t)uni((int)whdr[HX(t)].base);
     if (s == cap) {
-        uint32_t ncap = cap < 4 ? 8 : cap * 2;
+        uint32_t ncap = list_grown_cap(cap);
         if (w.pool_top + ncap > L.pool_cap) { w.status = MS_ST_ERR_POOL; return false; }
         uint32_t nb = w.pool_top;
         w.pool_top += ncap;
@@ -2798,6 +2799,30 @@ __global__ __launch_bounds__(MS_WAVE) void ms_core_model_kernel(MsLayout L, cons
     if (lane == 0) ((Gp<int32_t>)ok)[b] = bad ? 0 : 1;
 }
 
+// One clause under the level-0 assignment, for the kernels that attach clauses to a worker (ms_attach_kernel,
+// ms_rup_kernel): cl[b .. e), device literals, each variable at most once, 64 literals per round, one per lane.  sat: a
+// literal is TRUE; bad: one is out of range; else the free literals stand in learnt_buf[0 .. result), in clause order.
+template <bool LV>
+DEV int attach_scan(const Wk& w, const MsShared& sh, const MsLayout& L, Gp<const int32_t> cl, uint32_t b, uint32_t e,
+                    Gp<int32_t> learnt_buf, bool& sat, bool& bad) {
+    sat = false; bad = false;
+    int cnt = 0;
+    for (uint32_t k0 = b; k0 < e && !sat && !bad; k0 += MS_WAVE) {
+        const uint32_t k = k0 + (uint32_t)w.lane;
+        const bool in = k < e;
+        const int lit = in ? cl[k] : 0;
+        const bool ok = (uint32_t)lit < 2u * sh.n_vars;
+        const int v = in && ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_FALSE;   // units attached before are visible
+        bad = ballot(in && !ok) != 0;
+        sat = ballot(in && v == MS_VAL_TRUE) != 0;
+        const u64 free_m = ballot(in && v == MS_VAL_UNDEF);
+        if ((free_m >> w.lane) & 1) learnt_buf[cnt + popc64(free_m & lanemask_lt(w.lane))] = lit;
+        cnt += popc64(free_m);
+    }
+    wave_fence();
+    return cnt;
+}
+
 // ---- warm attach (incremental solve) ---------------------------------------------------
 // Clauses the caller added between two solves of one handle go to the workers that are still resident from the solve
 // before (mi355sat_set_incremental): one workgroup (one wave) per worker, between two slices.  Clause c is
@@ -2837,21 +2862,8 @@ __global__ __launch_bounds__(MS_WAVE) void ms_attach_kernel(MsShared sh, MsLayou
     Gp<int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
     for (uint32_t c = c0; c < c1 && w.status == MS_ST_RUNNING; c++) {
         const uint32_t b = (uint32_t)uni((int)co[c]), e = (uint32_t)uni((int)co[c + 1]);
-        bool sat = false, bad = false;
-        int cnt = 0;
-        for (uint32_t k0 = b; k0 < e && !sat && !bad; k0 += MS_WAVE) {
-            const uint32_t k = k0 + (uint32_t)w.lane;
-            const bool in = k < e;
-            const int lit = in ? cl[k] : 0;
-            const bool ok = (uint32_t)lit < 2u * sh.n_vars;
-            const int v = in && ok ? lit_value<false>(w, sh, L, lit) : MS_VAL_FALSE;   // units attached before are visible
-            bad = ballot(in && !ok) != 0;
-            sat = ballot(in && v == MS_VAL_TRUE) != 0;
-            const u64 free_m = ballot(in && v == MS_VAL_UNDEF);
-            if ((free_m >> w.lane) & 1) learnt_buf[cnt + popc64(free_m & lanemask_lt(w.lane))] = lit;
-            cnt += popc64(free_m);
-        }
-        wave_fence();
+        bool sat, bad;
+        const int cnt = attach_scan<false>(w, sh, L, cl, b, e, learnt_buf, sat, bad);
         if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
         if (sat) continue;
         if (cnt == 0) { w.status = MS_ST_UNSAT; break; }           // falsified at level 0
@@ -2859,4 +2871,157 @@ __global__ __launch_bounds__(MS_WAVE) void ms_attach_kernel(MsShared sh, MsLayou
         else if (add_learnt<false>(w, sh, L, cnt, 1u | MS_LBD_NOLOG) < 0) break;
     }
     wk_store<false>(w, sh, L, 0);
+}
+
+// ---- forward RUP check of a clausal proof (mi355sat_check_proof) -------------------------
+// Lemma i of a DRUP proof must follow from the formula and the lemmas before it by unit propagation alone: assume the
+// negation of its literals, propagate, expect a conflict - this kernel's hot loop, once per lemma, and the checks of
+// different parts of the proof do not depend on each other.  The host cuts the lemma list (the target clause is its last
+// entry) into contiguous segments, one per worker; worker w owns [a, b) and walks the lemmas 0 .. b-1:
+//   j >= a : check it.  Level 0 first - a conflict there means formula + lemmas before j are refuted by propagation alone
+//            (refuted_at = min(.., j)), every later lemma is RUP trivially and the worker is done.  Then one decision
+//            level: a TRUE literal ends the check (RUP), a FALSE one is skipped, the negation of every other one is
+//            enqueued, 64 literals per round; propagate; a fixpoint without conflict is first_failed = min(.., j).  The
+//            worker goes on either way: later lemmas are checked against the full prefix, as the sequential definition says.
+//            (An index the host marked as skipped still gets the level-0 propagation: it may be where the database falls.)
+//   always : attach it as ms_attach_kernel does under the level-0 assignment (satisfied: nothing; no free literal: the
+//            database is refuted from lemma j + 1 on; one: a level-0 fact left in the queue; else add_learnt with LBD 1,
+//            which no reduction ever drops).  The target is checked, never attached.
+// Deletion lines never reach the device: every clause in a worker's database is an original or a lemma, unit propagation
+// is monotone, so ignoring them is sound, and the verdict does not depend on the cut.  A lemma holding x and ~x is marked
+// on the host (skip[j]): never checked or attached.  No conflict is analysed, no clause is ever reduced away (the stores
+// are sized from the proof: a full one is MS_ST_ERR_*; the watch pool is laid out densely again when a list cannot grow).
+// State between launches, in the worker's script array: [0] cursor j, [1] a, [2] b, words 4-5 / 6-7 the 64-bit counts of
+// lemmas checked / attached.  A launch ends after prm.slice_conflicts lemmas or prm.slice_ticks.  Status when the worker
+// is done: MS_ST_SAT (through its segment) or MS_ST_UNSAT (database refuted).  mins[0] = first_failed, mins[1] =
+// refuted_at, both kept as their complements (a minimum is then one atomicMax, and a zeroed word means "none"): the only
+// words workers share, one atomic by one lane on the rare path.
+template <bool LV>
+__global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L, char* slabs, MsParams prm, const int32_t* lits,
+                                                        const uint32_t* offs, const uint8_t* skip, uint32_t n_items,
+                                                        unsigned long long* mins) {
+    __shared__ int32_t s_ring[MS_LDS_RING];
+    __shared__ uint32_t s_claim[MS_CLAIM_SLOTS];
+    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4 * MS_MAX_GROUPS < 64 ? 64 : 4 * MS_MAX_GROUPS];
+    __shared__ uint32_t s_tl[MS_WAVE];
+    __shared__ int32_t s_jd[2 * MS_MAX_GROUPS];
+    __shared__ int32_t s_bfl[MS_MAX_GROUPS];
+    __shared__ uint32_t s_ov;
+    __shared__ uint32_t s_mcnt;
+    HIP_DYNAMIC_SHARED(uint32_t, s_lval)
+    const uint32_t wid = blockIdx.x;
+    if (wid >= prm.n_workers) return;
+    Wk w;
+    w.lane = (int)threadIdx.x;
+    w.ring = (LdsI32)s_ring; w.claim = (LdsU32)s_claim; w.ov_cnt = (LdsU32)&s_ov; w.hist = (LdsU32)s_hist; w.lval = (LdsU32)s_lval; w.bfl = (LdsI32)s_bfl; w.tl = (LdsU32)s_tl; w.jd = (LdsI32)s_jd;
+    w.lseen = w.lval + ((sh.n_vars + 15) >> 4);   // (no analysis in this kernel; the level bitmaps are still maintained)
+    w.lcur = w.lseen + ((sh.n_vars + 31) >> 5);
+    w.lzero = w.lcur + ((sh.n_vars + 31) >> 5);
+    w.lfail = w.lzero + ((sh.n_vars + 31) >> 5);
+    w.lq = w.lfail + ((sh.n_vars + 31) >> 5);
+    w.mcnt = (LdsU32)&s_mcnt;
+    if (w.lane == 0) { s_ov = 0; s_mcnt = 0; }
+    wk_bind<LV>(w, sh, L, slabs + (size_t)wid * L.slab_bytes, prm);
+    wk_uniformize(w);
+    if (w.status != MS_ST_RUNNING) return;        // done in an earlier launch: nothing was changed, nothing to store
+    if (LV) { level_zero_rebuild(w, sh, L); cur_level_rebuild(w, sh, L); }
+    lds_fence();
+    const u64 t0 = __builtin_readcyclecounter();
+    const u64 tick0 = __builtin_amdgcn_s_memrealtime();
+    Gp<int32_t> cur = WK_PTR(int32_t, w, L, script);
+    Gp<const int32_t> cl = (Gp<const int32_t>)lits;
+    Gp<const uint32_t> co = (Gp<const uint32_t>)offs;
+    Gp<const uint8_t> sk = (Gp<const uint8_t>)skip;
+    Gp<int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
+    uint32_t j = (uint32_t)uni(cur[0]);
+    const uint32_t a = (uint32_t)uni(cur[1]);
+    uint32_t b = (uint32_t)uni(cur[2]);
+    if (b > n_items) b = n_items;
+    uint32_t n_checked = 0, n_attached = 0, budget = prm.slice_conflicts;
+    auto note_min = [&](int which, uint32_t idx) {
+        if (w.lane == 0) (void)atomicMax(&mins[which], ~(unsigned long long)idx);   // (the words hold complements)
+    };
+    for (; j < b && budget > 0 && w.status == MS_ST_RUNNING; j++, budget--) {
+        if (prm.slice_ticks && __builtin_amdgcn_s_memrealtime() - tick0 >= prm.slice_ticks) break;
+        // pool running low: collect the holes that grown lists left behind (the search's rule, on_fixpoint_body)
+        if (w.pool_top > L.pool_cap - L.pool_cap / 4) {
+            rebuild_watches(w, sh, L);
+            if (w.status != MS_ST_RUNNING) break;
+        }
+        const bool skipped = uni((int)sk[j]) != 0;    // x and ~x: RUP, never attached - but index j may be where it falls
+        const uint32_t lb = (uint32_t)uni((int)co[j]), le = (uint32_t)uni((int)co[j + 1]);
+        if (j >= a) {
+            if (propagate<LV>(w, sh, L)) {            // the level-0 queue
+                note_min(1, j);
+                w.status = MS_ST_UNSAT;
+                break;
+            }
+            if (w.status != MS_ST_RUNNING) break;
+        }
+        if (skipped) continue;
+        if (j >= a) {
+            n_checked++;
+            new_decision_level<LV>(w, sh, L);
+            bool rup = false, bad = false;
+            for (uint32_t k0 = lb; k0 < le && !rup && !bad; k0 += MS_WAVE) {
+                const uint32_t k = k0 + (uint32_t)w.lane;
+                const bool in = k < le;
+                const int lit = in ? cl[k] : 0;
+                const bool ok = (uint32_t)lit < 2u * sh.n_vars;
+                const int v = in && ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_FALSE;
+                bad = ballot(in && !ok) != 0;
+                rup = ballot(in && v == MS_VAL_TRUE) != 0;
+                if (bad || rup) break;
+                // (each variable at most once per lemma: the negations neither repeat nor clash)
+                wave_fence();
+                assign_winners<LV>(w, sh, L, in && v == MS_VAL_UNDEF, lit ^ 1, MS_REASON_NONE);
+                lds_fence();
+            }
+            if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
+            const bool confl = rup || propagate<LV>(w, sh, L);
+            cancel_until<LV>(w, sh, L, 0);
+            w.confl_kind = 0;
+            if (w.status != MS_ST_RUNNING) break;
+            if (!confl) note_min(0, j);
+        }
+        if (j + 1 >= n_items) continue;               // the target: checked only
+        n_attached++;
+        bool sat, bad;
+        const int cnt = attach_scan<LV>(w, sh, L, cl, lb, le, learnt_buf, sat, bad);
+        if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
+        if (sat) continue;
+        if (cnt == 0) {                               // falsified at level 0: refuted from the next lemma on
+            note_min(1, j + 1);
+            w.status = MS_ST_UNSAT;
+            j++;
+            break;
+        }
+        if (cnt == 1) { enqueue_uniform<LV>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE); continue; }
+        {   // A list that holds a large share of the proof asks for more than the quarter of the pool the rule above keeps
+            // free: if the two pushes of this clause could not both grow their lists (list_push_uniform's policy), lay the
+            // lists out densely first - every list then has two free slots at least, and the dense layout always fits
+            // (build_layout_and_template's dense_max).
+            Gp<const MsWatchHdr> whdr = WKA(MsWatchHdr, whdr);
+            uint32_t need = 0;
+            for (int k = 0; k < 2; k++) {
+                const int t = uni(learnt_buf[k]) ^ 1;
+                const uint32_t sz = (uint32_t)uni((int)whdr[HX(t)].size), cap = (uint32_t)uni((int)whdr[HX(t)].cap);
+                if (sz >= cap) need += list_grown_cap(cap);
+            }
+            if ((u64)w.pool_top + need > (u64)L.pool_cap) {
+                rebuild_watches(w, sh, L);
+                if (w.status != MS_ST_RUNNING) break;
+            }
+        }
+        if (add_learnt<LV>(w, sh, L, cnt, 1u | MS_LBD_NOLOG) < 0) break;
+    }
+    if (w.status == MS_ST_RUNNING && j >= b) w.status = MS_ST_SAT;
+    wave_fence();
+    if (w.lane == 0) {
+        cur[0] = (int32_t)j;
+        Gp<u64> cnt64 = (Gp<u64>)(cur + 4);
+        cnt64[0] += n_checked;
+        cnt64[1] += n_attached;
+    }
+    wk_store<LV>(w, sh, L, __builtin_readcyclecounter() - t0);
 }

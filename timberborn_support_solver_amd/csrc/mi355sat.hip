@@ -33,7 +33,7 @@ double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-struct HipErr { std::string msg; };
+struct HipErr { std::string msg; int code = MI355SAT_ERR_HIP; };
 #define HIPCHK(x)                                                                                   \
     do {                                                                                            \
         hipError_t e_ = (x);                                                                        \
@@ -410,6 +410,7 @@ struct mi355sat {
     // a SAT answer; test hook (mi355sat_debug_core_min_round): at most this many candidates per round, 0 = the default
     uint64_t sat_clauses = UINT64_MAX;         // stats.n_clauses when a solve / batch last answered SAT
     uint32_t core_min_round = 0;
+    uint32_t proof_chunk = 0;                  // test hook (mi355sat_debug_proof_check_chunk): lemmas per worker and launch of a proof check
     // warm incremental solve (mi355sat_set_incremental): what the last mi355sat_solve() left on the device, and what was
     // attached to it since
     struct Incremental {
@@ -510,7 +511,7 @@ int guarded(mi355sat* s, GuardKind kind, F&& body) {
         rc = body();
     } catch (HipErr& he) {
         s->err = he.msg;
-        rc = MI355SAT_ERR_HIP;
+        rc = he.code;
     } catch (std::bad_alloc&) {
         s->err = "out of host memory";
         rc = MI355SAT_ERR_OOM;
@@ -710,7 +711,8 @@ void propagate_units(Formula& F) {
 }
 
 // Device form of the formula: variable order, binary / ternary CSRs, long clauses.
-void build_csr(const mi355sat& s, const Formula& F, bool units_propagated, Prepared& P) {
+// identity_order: the caller's variable order whatever opts.var_order says (the proof checker's trusted base).
+void build_csr(const mi355sat& s, const Formula& F, bool units_propagated, Prepared& P, bool identity_order = false) {
     const uint32_t nv = F.nv;
     P.n_vars = nv;
     P.unsat = F.unsat;
@@ -721,7 +723,7 @@ void build_csr(const mi355sat& s, const Formula& F, bool units_propagated, Prepa
     const std::vector<uint64_t>& no = F.no;
     const size_t nn = F.n_clauses();
     // device variable order
-    if (s.opts.var_order > 0) locality_order(nv, nl, no, F.val, P.perm);
+    if (s.opts.var_order > 0 && !identity_order) locality_order(nv, nl, no, F.val, P.perm);
     else { P.perm.resize(nv); for (uint32_t v = 0; v < nv; v++) P.perm[v] = v; }
     for (auto& l : nl) l = 2 * (int32_t)P.perm[l >> 1] | (l & 1);
     for (auto& l : P.units) l = 2 * (int32_t)P.perm[l >> 1] | (l & 1);
@@ -776,16 +778,17 @@ void build_csr(const mi355sat& s, const Formula& F, bool units_propagated, Prepa
     }
 }
 
-void prepare(const mi355sat& s, bool simplify, Prepared& P) {
+void prepare(const mi355sat& s, bool simplify, Prepared& P, bool identity_order = false) {
     Formula F;
     normalise(s, F);
     if (simplify) propagate_units(F);
-    build_csr(s, F, simplify, P);
+    build_csr(s, F, simplify, P, identity_order);
 }
 
 // ---- slab template -----------------------------------------------------------------
+// learnt_cap / learnt_lit_cap: 0 = the rule below (what a search wants); the proof checker sizes both stores from its proof.
 void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_t script_cap,
-                               std::vector<char>& tmpl) {
+                               std::vector<char>& tmpl, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0) {
     const uint32_t nv = P.n_vars, no = (uint32_t)P.cl_hdr.size();
     MsLayout& L = s.L;
     memset(&L, 0, sizeof L);
@@ -796,6 +799,8 @@ void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_c
     L.learnt_cap = (uint32_t)std::min<uint64_t>(1u << 17, std::max<uint64_t>(1u << 15, 2 * (uint64_t)no + 4096));
     // (round 2: 2 M literals at most instead of 4 M - a store that runs full reduces early, add_learnt / on_conflict)
     L.learnt_lit_cap = (uint32_t)std::min<uint64_t>(2u << 20, std::max<uint64_t>(1u << 19, 6 * base_lits));
+    if (learnt_cap) L.learnt_cap = learnt_cap;
+    if (learnt_lit_cap) L.learnt_lit_cap = learnt_lit_cap;
     L.vm_cap = 3 * nv + 256;
     L.assump_cap = assump_cap;
     L.script_cap = script_cap;
@@ -900,10 +905,10 @@ void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_c
 void set_error(mi355sat* s, const std::string& m) { s->err = m; }
 
 void upload_formula(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_t script_cap, uint32_t want_workers,
-                    uint32_t initial_workers = 0) {
+                    uint32_t initial_workers = 0, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0, int no_room_code = MI355SAT_ERR_HIP) {
     HIPCHK(hipSetDevice(s.device));
     std::vector<char> tmpl;
-    build_layout_and_template(s, P, assump_cap, script_cap, tmpl);
+    build_layout_and_template(s, P, assump_cap, script_cap, tmpl, learnt_cap, learnt_lit_cap);
     s.n_vars = P.n_vars;
     s.perm = P.perm;
     s.d_cl_lits.upload(P.cl_lits, s.stream);
@@ -925,7 +930,7 @@ void upload_formula(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     free_b += SlabBuf::cached_bytes(s.device);   // a parked slab buffer of an earlier handle is ours to reuse
     uint64_t fit = (uint64_t)((double)free_b * 0.85) / (s.L.slab_bytes * 1ull);
-    if (fit < 2) throw HipErr{"not enough device memory for one worker slab"};
+    if (fit < 2) throw HipErr{"not enough device memory for one worker slab", no_room_code};
     uint32_t W = (uint32_t)std::min<uint64_t>(want_workers, fit - 1);
     if (W == 0) W = 1;
     s.n_workers = W;
@@ -2708,6 +2713,235 @@ int minimize_core_impl(mi355sat* s, Core& core, int64_t conflict_budget, mi355sa
     return rc;
 }
 
+
+// ---- DRUP proof check (mi355sat_check_proof) --------------------------------------------------------------------------
+// Host side of ms_rup_kernel: the proof as lemmas (the target last), validated against the handle's variables before
+// anything is uploaded; the formula prepared WITHOUT simplification in the caller's variable order (the trusted base);
+// the slab's learnt store sized from the proof; one contiguous segment of the lemma list per worker; launches until every
+// worker is done, the interrupt flag polled between them.  DESIGN.md §4.
+struct ProofLemmas {
+    std::vector<int32_t> lits;         // DIMACS literals of all lemmas, then the target's
+    std::vector<uint64_t> offs{0};     // n_lemmas + 2 entries once the target is appended
+    uint64_t n_lemmas = 0, n_deletions = 0;
+};
+
+// proof: flat words (mi355sat.h).  Returns 0 or MI355SAT_ERR_ARG with a text.
+int parse_proof_words(mi355sat& s, const int32_t* proof, uint64_t n_words, ProofLemmas& out) {
+    uint64_t i = 0;
+    while (i < n_words) {
+        const bool del = proof[i] == INT32_MIN;
+        if (del) i++;
+        const uint64_t st = i;
+        while (i < n_words && proof[i] != 0) {
+            if (proof[i] == INT32_MIN) { s.err = "proof: a deletion marker inside a clause"; return MI355SAT_ERR_ARG; }
+            if (var_of(proof[i]) > s.max_var) { s.err = "proof: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
+            i++;
+        }
+        if (i == n_words) { s.err = "proof: the last clause is not terminated"; return MI355SAT_ERR_ARG; }
+        if (del) out.n_deletions++;
+        else {
+            out.lits.insert(out.lits.end(), proof + st, proof + i);
+            out.offs.push_back(out.lits.size());
+            out.n_lemmas++;
+        }
+        i++;   // the 0
+    }
+    return 0;
+}
+
+// DRUP text -> flat words as dimacs.read_drup makes them.
+int read_proof_file(mi355sat& s, const char* path, std::vector<int32_t>& words) {
+    FILE* f = fopen(path, "r");
+    if (!f) { s.err = std::string("cannot open proof file ") + path; return MI355SAT_ERR_ARG; }
+    std::string text;
+    char buf[1 << 16];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+    fclose(f);
+    const char* p = text.c_str();
+    bool line_start = true, open_clause = false;
+    for (;;) {
+        while (*p == ' ' || *p == '\t' || *p == '\r') p++;
+        if (*p == '\n') { p++; line_start = true; continue; }
+        if (!*p) break;
+        if (*p == 'd' && line_start && !open_clause) { words.push_back(INT32_MIN); p++; line_start = false; open_clause = true; continue; }
+        char* end = nullptr;
+        const long long v = strtoll(p, &end, 10);
+        if (end == p || v <= INT32_MIN || v > INT32_MAX) { s.err = std::string("malformed proof file ") + path; return MI355SAT_ERR_ARG; }
+        words.push_back((int32_t)v);
+        open_clause = v != 0;
+        line_start = false;
+        p = end;
+    }
+    return 0;
+}
+
+SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32_t* lits, const uint32_t* offs, const uint8_t* skip,
+                       uint32_t n_items, unsigned long long* mins) {
+    MsParams prm{};
+    prm.n_workers = active;
+    prm.max_groups = s.opts.max_groups > 0 ? s.opts.max_groups : MS_MAX_GROUPS;
+    prm.slice_conflicts = chunk ? chunk : 0xffffffffu;         // lemmas per worker and launch
+    prm.slice_ticks = chunk ? 0 : 20ull * 100000ull;           // ... or 20 ms
+    prm.stop_flag = s.stop_flag;
+    const mi355sat_search_build build = choose_build(active, s.lds_val_bytes, s.lds_val, s.opts.lds_val, s.opts.one_per_simd, 1);
+    HIPCHK(hipEventRecord(s.ev0, s.stream));
+    if (build.lds) hipLaunchKernelGGL(ms_rup_kernel<true>, dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins);
+    else hipLaunchKernelGGL(ms_rup_kernel<false>, dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s.ev1, s.stream));
+    HIPCHK(hipEventSynchronize(s.ev1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+    s.stats.kernel_seconds += ms * 1e-3;
+    s.stats.kernel_launches++;
+    return SliceResult{ms};
+}
+
+int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info) {
+    for (uint64_t i = 0; i < n_target; i++) {
+        if (target[i] == 0 || target[i] == INT32_MIN) { s.err = "proof target: literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
+        if (var_of(target[i]) > s.max_var) { s.err = "proof target: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
+    }
+    if (pf.n_lemmas + 2 > 0x7fffffffull || pf.lits.size() + n_target + 5 * (pf.n_lemmas + 2) > 0x7ffffff0ull) {
+        s.err = "proof too large for a worker's clause store";
+        return MI355SAT_ERR_OOM;
+    }
+    pf.lits.insert(pf.lits.end(), target, target + n_target);
+    pf.offs.push_back(pf.lits.size());
+    const uint32_t n_items = (uint32_t)pf.n_lemmas + 1;       // the target is lemma number n_lemmas
+    info.n_lemmas = pf.n_lemmas;
+    info.n_deletions_ignored = pf.n_deletions;
+    info.first_failed = info.refuted_at = UINT64_MAX;
+    if (s.interrupted.load()) {      // as a solve: an interrupt that came before the call stops it at once
+        consume_interrupt(s);
+        info.valid = -1;
+        return MI355SAT_INTERRUPTED;
+    }
+    go_cold(s, MI355SAT_COLD_OTHER_SEARCH);      // (the slabs become this check's)
+    s.ph.on_device = false;
+    Prepared P;
+    prepare(s, /*simplify=*/false, P, /*identity_order=*/true);
+    if (P.unsat) {               // an empty clause or contradictory units among the caller's clauses
+        info.refuted_at = 0;
+        info.valid = 1;
+        return 0;
+    }
+    if (P.n_vars == 0) {         // no variable, no clause: only empty lemmas are possible, and none is RUP
+        info.first_failed = 0;
+        info.valid = 0;
+        return 0;
+    }
+    // the proof as the device reads it: device literals, each variable at most once per lemma; x and ~x: skipped
+    std::vector<int32_t> dl;
+    std::vector<uint32_t> doff{0};
+    std::vector<uint8_t> skip(n_items, 0);
+    dl.reserve(pf.lits.size() + 4);
+    uint64_t store_lits = 0;
+    // (the lemma's own literal order is kept - a solver writes the asserting literal first, and the first two free literals
+    // become the watches: sorted, the lists of the lowest variables would hold most of the proof)
+    std::vector<int32_t> tmp;
+    std::vector<uint32_t> stamp(P.n_vars, 0);       // per variable: 2 * (j + 1) | sign of its literal in lemma j
+    for (uint32_t j = 0; j < n_items; j++) {
+        tmp.clear();
+        for (uint64_t k = pf.offs[j]; k < pf.offs[j + 1]; k++) {
+            const int32_t l = to_device(P.perm, pf.lits[k]);
+            uint32_t& st = stamp[l >> 1];
+            if ((st >> 1) != j + 1) { st = 2 * (j + 1) | (uint32_t)(l & 1); tmp.push_back(l); }
+            else if ((st & 1u) != (uint32_t)(l & 1)) skip[j] = 1;
+        }
+        if (skip[j]) tmp.clear();
+        dl.insert(dl.end(), tmp.begin(), tmp.end());
+        doff.push_back((uint32_t)dl.size());
+        if (j + 1 < n_items) store_lits += (tmp.size() + 3) & ~(size_t)3;
+    }
+    for (int k = 0; k < 4; k++) dl.push_back(0);
+    // a worker's learnt store: every lemma, each 16-byte aligned (add_learnt wants 8 words of headroom)
+    const uint32_t learnt_cap = (uint32_t)pf.n_lemmas + 1;
+    const uint32_t learnt_lit_cap = (uint32_t)(store_lits + 16);
+    uint32_t S = segments ? segments : fleet_size(s);
+    S = std::min(S, n_items);
+    upload_formula(s, P, 0, /*script_cap=*/8, S, 0, learnt_cap, learnt_lit_cap, MI355SAT_ERR_OOM);
+    S = std::min(S, s.n_workers);                // (what device memory holds)
+    s.n_workers = s.n_alloc = S;
+    info.segments = info.workers = S;
+    std::vector<int32_t> script;                 // per worker: cursor, a, b, pad, checked (64 bit), attached (64 bit)
+    std::vector<uint64_t> soff{0};
+    for (uint32_t w = 0; w < S; w++) {
+        const int32_t a = (int32_t)((uint64_t)n_items * w / S), b = (int32_t)((uint64_t)n_items * (w + 1) / S);
+        script.insert(script.end(), {0, a, b, 0, 0, 0, 0, 0});
+        soff.push_back(script.size());
+    }
+    reset_workers(s);
+    customize(s, nullptr, nullptr, &script, &soff, S);
+    DevBuf<int32_t> d_lits;
+    DevBuf<uint32_t> d_offs;
+    DevBuf<uint8_t> d_skip;
+    DevBuf<unsigned long long> d_mins;
+    d_lits.upload(dl, s.stream);
+    d_offs.upload(doff, s.stream);
+    d_skip.upload(skip, s.stream);
+    d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
+    HIPCHK(hipStreamSynchronize(s.stream));
+    const uint32_t chunk = s.proof_chunk;
+    const double k0 = s.stats.kernel_seconds;
+    std::vector<MsState> sts;
+    bool interrupted = false;
+    for (;;) {
+        if (s.interrupted.load()) { interrupted = true; break; }
+        launch_rup(s, S, chunk, d_lits.p, d_offs.p, d_skip.p, n_items, d_mins.p);
+        info.launches++;
+        gather_states(s, sts);
+        bool running = false;
+        for (uint32_t w = 0; w < S; w++) {
+            if (sts[w].status < 0) {
+                s.err = std::string("proof check: ") + status_text(sts[w].status);
+                return sts[w].status == MS_ST_ERR_INTERNAL ? MI355SAT_ERR_HIP : MI355SAT_ERR_OOM;
+            }
+            running = running || sts[w].status == MS_ST_RUNNING;
+        }
+        if (!running) break;
+    }
+    info.kernel_seconds = s.stats.kernel_seconds - k0;
+    for (const MsState& st : sts) info.propagations += st.propagations;
+    if (info.launches) {
+        std::vector<int32_t> sc((size_t)S * 8);
+        HIPCHK(hipMemcpy2D(sc.data(), 32, s.d_slabs.p + s.L.script, s.L.slab_bytes, 32, S, hipMemcpyDeviceToHost));
+        for (uint32_t w = 0; w < S; w++) {
+            uint64_t c[2];
+            memcpy(c, &sc[(size_t)w * 8 + 4], sizeof c);
+            info.lemmas_checked += c[0];
+            info.lemmas_attached += c[1];
+        }
+    }
+    if (interrupted) {
+        consume_interrupt(s);
+        info.valid = -1;
+        return MI355SAT_INTERRUPTED;
+    }
+    unsigned long long mins[2];
+    HIPCHK(hipMemcpy(mins, d_mins.p, sizeof mins, hipMemcpyDeviceToHost));
+    info.first_failed = ~mins[0];
+    info.refuted_at = ~mins[1];
+    // (a lemma behind the point of refutation is RUP whatever a worker that had not seen the refuting lemmas yet made of it:
+    // a worker checks lemma j against ALL lemmas before j, so there is no such worker - kept as a cross-check)
+    if (info.first_failed != UINT64_MAX && info.refuted_at <= info.first_failed) {
+        s.err = "proof check: a lemma failed behind the point of refutation";
+        return MI355SAT_ERR_HIP;
+    }
+    info.valid = info.first_failed == UINT64_MAX ? 1 : 0;
+    return 0;
+}
+
+int check_proof_entry(mi355sat* s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info* out) {
+    mi355sat_proof_info info{};
+    const double t0 = now_s();
+    const int rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info); });
+    info.seconds = now_s() - t0;
+    if (rc < 0) go_cold(*s, MI355SAT_COLD_FIRST);
+    *out = info;
+    return rc;
+}
+
 }  // namespace
 
 struct SweepHolder { Sweep sw; mi355sat_stats_t base; };
@@ -2962,6 +3196,36 @@ int mi355sat_debug_phases(const mi355sat* s, mi355sat_phase_info* out) {
 int mi355sat_set_proof_path(mi355sat* s, const char* path) {
     if (!s) return MI355SAT_ERR_ARG;
     s->proof_path = path ? path : "";
+    return 0;
+}
+
+int mi355sat_check_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
+                         uint32_t segments, mi355sat_proof_info* out) {
+    if (!s || !out || (n_words && !proof) || (n_target && !target)) return MI355SAT_ERR_ARG;
+    if (s->sweep) { s->err = "check_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = "check_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    ProofLemmas pf;
+    if (int rc = guarded(s, GUARD_HOST, [&] { return parse_proof_words(*s, proof, n_words, pf); })) return rc;
+    return check_proof_entry(s, pf, target, n_target, segments, out);
+}
+
+int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
+                              mi355sat_proof_info* out) {
+    if (!s || !out || !path || (n_target && !target)) return MI355SAT_ERR_ARG;
+    if (s->sweep) { s->err = "check_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = "check_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    ProofLemmas pf;
+    if (int rc = guarded(s, GUARD_HOST, [&] {
+            std::vector<int32_t> words;
+            if (int e = read_proof_file(*s, path, words)) return e;
+            return parse_proof_words(*s, words.data(), words.size(), pf);
+        })) return rc;
+    return check_proof_entry(s, pf, target, n_target, segments, out);
+}
+
+int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->proof_chunk = max_lemmas_per_launch;
     return 0;
 }
 

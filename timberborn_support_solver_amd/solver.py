@@ -104,6 +104,23 @@ class Mi355SatCoreMinInfo(ctypes.Structure):   # mi355sat_core_min_info
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatProofInfo(ctypes.Structure):   # mi355sat_proof_info
+    _fields_ = [("valid", ctypes.c_int32), ("pad", ctypes.c_int32)] + \
+               [(n, ctypes.c_uint64) for n in ("n_lemmas", "n_deletions_ignored", "first_failed", "refuted_at", "segments",
+                                               "workers", "lemmas_checked", "lemmas_attached", "propagations", "launches")] + \
+               [("seconds", ctypes.c_double), ("kernel_seconds", ctypes.c_double)]
+
+    def as_dict(self):
+        """first_failed / refuted_at: None where the C struct says UINT64_MAX (no such lemma); interrupted: the check was
+        stopped and there is no verdict (valid = -1)."""
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+        for k in ("first_failed", "refuted_at"):
+            if d[k] == 2 ** 64 - 1:
+                d[k] = None
+        d["interrupted"] = d["valid"] < 0
+        return d
+
+
 class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
     NONE = 0
     FIRST = 1
@@ -170,6 +187,9 @@ def _bind(L):
     L.mi355sat_debug_last_search_build.argtypes = [vp, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_debug_search_build_rule.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
+    L.mi355sat_check_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
+    L.mi355sat_check_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
+    L.mi355sat_debug_proof_check_chunk.argtypes = [vp, ctypes.c_uint32]
     L.mi355sat_set_incremental.argtypes = [vp, ctypes.c_int]
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
@@ -314,6 +334,33 @@ class Mi355Sat:
     def debug_core_min_round(self, max_candidates=0):
         """Test hook: at most max_candidates candidates per round of minimize_core (0 = the default)."""
         self._check(self._L.mi355sat_debug_core_min_round(self._h, int(max_candidates)), "debug_core_min_round")
+
+    # ---- certificates: DRUP proofs checked on the device (include/mi355sat.h)
+    def check_proof(self, proof, target=(), segments=0):
+        """Forward RUP check (deletion lines ignored) of `proof` - flat int32, lemmas 0-terminated, as dimacs.read_drup
+        returns it - against this handle's clauses; `target` is the clause it must derive (default: the empty clause; for
+        a solve under assumptions the negated core).  segments: into how many parts the lemma list is cut, one wavefront
+        each (0 = the default); the verdict does not depend on it.  Returns mi355sat_proof_info as a dict: "valid" is the
+        verdict, "first_failed" / "refuted_at" are None where there is no such lemma, "interrupted" is True (and "valid"
+        -1) if an interrupt ended the check."""
+        pr = np.ascontiguousarray(proof, dtype=np.int32)
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatProofInfo()
+        self._check(self._L.mi355sat_check_proof(self._h, _p(pr), pr.size, _p(tg), tg.size, int(segments), ctypes.byref(info)),
+                    "check_proof")
+        return info.as_dict()
+
+    def check_proof_file(self, path, target=(), segments=0):
+        """The same for a DRUP text file as set_proof_path() writes it."""
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatProofInfo()
+        self._check(self._L.mi355sat_check_proof_file(self._h, str(path).encode(), _p(tg), tg.size, int(segments),
+                                                      ctypes.byref(info)), "check_proof_file")
+        return info.as_dict()
+
+    def debug_proof_check_chunk(self, max_lemmas_per_launch=0):
+        """Test hook: at most this many lemmas per worker and launch of check_proof (0 = the default, time-bounded)."""
+        self._check(self._L.mi355sat_debug_proof_check_chunk(self._h, int(max_lemmas_per_launch)), "debug_proof_check_chunk")
 
     # ---- phase hints (rustsat PhaseLit's place; seeded, not forced: include/mi355sat.h)
     def phase(self, lit):
