@@ -481,6 +481,45 @@ int mi355sat_debug_heuristics(const mi355sat* s, mi355sat_heuristics_info* out);
  * predecessor (2000).  0 keeps the default; the two periods are at most 65535.  Takes effect with the next solve. */
 int mi355sat_debug_set_schedule(mi355sat* s, uint32_t first_vivify, uint32_t vivify_every, uint32_t rephase_every);
 
+/* --- when a device store is full ------------------------------------------- */
+/* Every worker has four stores of fixed size, laid out at a cold start: learnt-clause slots, learnt literals, the watch
+ * pool and (with a proof path) its proof log.  The default sizes are thousands of times what a short solve needs.
+ *   - Learnt store (slots or literals): a worker reduces its clause database early once either passes 7/8 of its
+ *     capacity, and again on the spot when a clause finds the store full.  A reduction keeps binary clauses, clauses of
+ *     LBD <= 2, clauses used since the last reduction with LBD <= 6 and the reasons of assigned literals.  If nothing
+ *     could go, a clause the worker learnt itself (or one the caller added warm) ends the solve: MI355SAT_ERR_OOM, "device
+ *     learnt-clause store exhausted".  A clause received from another worker (the exchange, mi355sat_share_import) is
+ *     optional and never ends a solve: it is attached only while a quarter of the slots and of the literal words stays
+ *     free (one of three and more literals: only while the slots are at most half full); otherwise it is passed over
+ *     (three quarters full: counted, imports_dropped_full below) and the solve goes on.
+ *   - Watch pool: lists that outgrow their slot move to the top of the pool; the holes are collected at every reduction
+ *     and whenever the top passes 3/4 of the pool.  A list that cannot grow, or a collection that does not fit, ends the
+ *     solve: MI355SAT_ERR_OOM, "device watch pool exhausted".
+ *   - Proof log (drained after every slice): lemmas fill it from the bottom, deletion lines from the top; deletion lines
+ *     that do not fit are left out, and those in the way of a lemma are given up - the proof stays valid without them.
+ *     Only when the lemmas of one slice alone do not fit does the solve end: MI355SAT_ERR_OOM, "proof buffer overflow
+ *     ..."; the proof file is closed, truncated.  In the file a slice's deletion lines follow its lemmas.
+ * After any of these the handle is usable: failed / core answer MI355SAT_ERR_STATE, and the next solve starts cold
+ * (MI355SAT_COLD_FIRST with the incremental mode on).  During a warm attach a full store is no error: that solve starts
+ * cold instead (MI355SAT_COLD_DEVICE_FULL).
+ *
+ * Test hooks: the sizes of those stores.  mi355sat_debug_set_capacities() replaces the sizing rules from the next cold start
+ * of mi355sat_solve / _solve_batch / _sweep_begin / _minimize_core on (mi355sat_check_proof keeps sizing its stores from the
+ * proof; mi355sat_propagate_batch keeps the rules); each argument 0 = the rule.  learnt_cap: clause slots per worker, 4 ..
+ * 2^17; learnt_lit_cap: literal words, 64 .. 2^21; pool_slack: the watch pool is the initial lists (pool_initial below)
+ * plus that many entries, at most 2^30; proof_cap: words per worker, 8 .. 2^23.  Anything else: MI355SAT_ERR_ARG.  Workers
+ * that are resident (incremental mode) keep the layout they have. */
+int mi355sat_debug_set_capacities(mi355sat* s, uint32_t learnt_cap, uint32_t learnt_lit_cap, uint32_t pool_slack, uint32_t proof_cap);
+typedef struct mi355sat_capacity_info {
+    uint32_t learnt_cap, learnt_lit_cap, pool_cap, pool_initial, proof_cap, assump_cap, vm_cap, pad;
+    uint64_t pressure_reduces;     /* reduce_db runs that conflicts did not make due: the 7/8 rule and add_learnt's inline one */
+    uint64_t pool_rebuilds;        /* rebuild_watches because pool_top passed 3/4 of pool_cap */
+    uint64_t imports_dropped_full; /* exchanged records passed over because the store had no room to spare */
+} mi355sat_capacity_info;
+/* The layout of the last cold start of a search (proof_cap 0: no proof was logged) and the three counts summed over the
+ * workers of the last solve / batch / sweep; MI355SAT_ERR_STATE before the first cold start. */
+int mi355sat_debug_capacities(const mi355sat* s, mi355sat_capacity_info* out);
+
 /* Clause exchange BETWEEN handles that search the SAME formula - the replicas of the sharded loop's last bounds, one
  * handle per GPU (every rank poses the reference's next bound, crates/repl/src/main.rs:292-295, with its own
  * seed).  Inside one handle the workers pass their short / low-LBD learnt clauses on through a ring on the device;

@@ -1805,16 +1805,27 @@ DEV void reduce_db(Wk& w, const MsShared& sh, const MsLayout& L, LoopState* pls 
     wave_fence();
 }
 
-// Store the clause in learnt_buf[0..n) and attach it.  Returns its cref (or -1).
+DEV bool learnt_store_full(const Wk& w, const MsLayout& L, int n) {
+    return w.n_learnts >= L.learnt_cap || w.lc_lits_n + (uint32_t)n + 8 > L.learnt_lit_cap;
+}
+// Room for a clause of n literals in the learnt store: a store that is full before the scheduled reduction is reduced now
+// (the state is consistent at every call site; learnt_buf is not touched).  False if the reduction freed nothing - every
+// clause protected: binary, LBD <= 2, locked - or failed itself (w.status tells which).
+template <bool LV>
+DEV bool learnt_make_room(Wk& w, const MsShared& sh, const MsLayout& L, int n, LoopState* pls) {
+    if (!learnt_store_full(w, L, n)) return true;
+    if (w.lane == 0) WK_PTR(MsState, w, L, state)->n_pressure_reduces++;
+    reduce_db<LV>(w, sh, L, pls);
+    return w.status == MS_ST_RUNNING && !learnt_store_full(w, L, n);
+}
+
+// Store the clause in learnt_buf[0..n) and attach it.  Returns its cref (or -1).  A clause the worker cannot do without
+// - one it learnt itself, one the caller added - that finds no room even after a reduction ends in MS_ST_ERR_LEARNT.
 template <bool LV>
 DEV int add_learnt(Wk& w, const MsShared& sh, const MsLayout& L, int n, uint32_t lbd, LoopState* pls = nullptr) {
-    if (w.n_learnts >= L.learnt_cap || w.lc_lits_n + (uint32_t)n + 8 > L.learnt_lit_cap) {
-        reduce_db<LV>(w, sh, L, pls);  // store full before the scheduled reduction: reduce now (state is consistent here)
-        if (w.status != MS_ST_RUNNING) return -1;
-        if (w.n_learnts >= L.learnt_cap || w.lc_lits_n + (uint32_t)n + 8 > L.learnt_lit_cap) {
-            w.status = MS_ST_ERR_LEARNT;
-            return -1;
-        }
+    if (!learnt_make_room<LV>(w, sh, L, n, pls)) {
+        if (w.status == MS_ST_RUNNING) w.status = MS_ST_ERR_LEARNT;
+        return -1;
     }
     Gp<const int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
     Gp<int32_t> lc_lits = WK_PTR(int32_t, w, L, lc_lits);
@@ -1951,7 +1962,24 @@ struct LoopState {
     double restart_k;          // Glucose's K: restart when the recent LBD average times K exceeds the global one
 };
 
-// DRUP deletion lines (-2, literals, -1) for the lanes' dropped clauses, appended to the worker's log.
+// A worker's proof log has two ends.  Lemmas grow from word 0 upwards (proof_len[0] words, counted on even when they no
+// longer fit: the host fails the solve on proof_len[0] > proof_cap), deletion lines from the top downwards (proof_len[1]
+// words).  A deletion line is optional and a lemma is not: one that needs the room the deletion lines took discards
+// them, so that a log fails a solve only when the slice's lemmas alone do not fit.  The host writes the lemmas first and
+// the deletion lines behind them - later than the reduction happened, which a checker can only profit from.
+// Where the n_words of a lemma (terminator included) go, or 0xffffffff if the log cannot hold them.
+DEV uint32_t proof_lemma_slot(Wk& w, LoopState& ls, uint32_t n_words) {
+    const uint32_t o = (uint32_t)uni((int)ls.proof_len[0]), del = (uint32_t)uni((int)ls.proof_len[1]);
+    const bool fits = o + n_words <= ls.proof_cap;
+    if (w.lane == 0) {
+        if (fits && o + n_words > ls.proof_cap - del) ls.proof_len[1] = 0;
+        ls.proof_len[0] = o + n_words;
+    }
+    wave_fence();
+    return fits ? o : 0xffffffffu;
+}
+
+// DRUP deletion lines (-2, literals, -1) for the lanes' dropped clauses, at the upper end of the worker's log.
 DEV void proof_log_deletions(Wk& w, const MsLayout& L, LoopState* pls, bool dl, uint32_t o0, uint32_t len) {
     if (!pls->proof_buf || ballot(dl) == 0) return;
     const uint32_t need = dl ? len + 2 : 0;
@@ -1960,17 +1988,18 @@ DEV void proof_log_deletions(Wk& w, const MsLayout& L, LoopState* pls, bool dl, 
         const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
         if (w.lane >= o) incl += t;
     }
-    const uint32_t total = (uint32_t)bcast((int)incl, 63), base = (uint32_t)uni((int)*pls->proof_len);
-    if (base + total > pls->proof_cap) return;      // no room: deletion lines are optional (a lost LEMMA fails the solve)
+    const uint32_t total = (uint32_t)bcast((int)incl, 63);
+    const uint32_t lemmas = (uint32_t)uni((int)pls->proof_len[0]), used = (uint32_t)uni((int)pls->proof_len[1]);
+    if ((u64)lemmas + used + total > pls->proof_cap) return;      // no room: deletion lines are optional
     if (dl) {
-        Gp<int32_t> out = pls->proof_buf + base + (incl - need);
+        Gp<int32_t> out = pls->proof_buf + (pls->proof_cap - used - total) + (incl - need);
         Gp<const int32_t> lits = WK_PTR(int32_t, w, L, lc_lits) + o0;
         out[0] = -2;
         for (uint32_t j = 0; j < len; j++) out[1 + j] = lits[j];
         out[1 + len] = -1;
     }
     wave_fence();
-    if (w.lane == 0) *pls->proof_len = base + total;
+    if (w.lane == 0) pls->proof_len[1] = used + total;
     wave_fence();
 }
 
@@ -2012,7 +2041,7 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
     Gp<int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
     Gp<const int32_t> pool = (Gp<const int32_t>)ls.share_pool;
     int budget = 4096;   // records per call; the rest waits for the next restart
-    uint32_t skipped = 0;
+    uint32_t skipped = 0, dropped = 0;
     for (; pos < end && budget > 0 && w.status == MS_ST_RUNNING; pos++, budget--) {
         // one record per step, one literal per lane (records are 128 bytes: one coalesced load)
         const int word = pool[(pos % ls.share_slots) * MS_SHARE_REC + (u64)(w.lane & (MS_SHARE_REC - 1))];
@@ -2032,6 +2061,13 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
             ls.n_imported_units++;
         } else {
             if (w.n_learnts > L.learnt_cap / 2 && cnt > 2) continue;   // store half full: only binaries
+            // An exchanged clause is optional, and one of two literals is never reduced away: it goes in only while that
+            // leaves a quarter of the store to the worker's own clauses - which end the solve when they find no room
+            // (add_learnt).  So an import never meets a full store, and never reduces in the middle of this loop.
+            if (w.n_learnts >= L.learnt_cap - L.learnt_cap / 4 || w.lc_lits_n + (uint32_t)cnt + 8 > L.learnt_lit_cap - L.learnt_lit_cap / 4) {
+                dropped++;
+                continue;
+            }
             if ((free_m >> w.lane) & 1) learnt_buf[popc64(free_m & lanemask_lt(w.lane))] = word;
             wave_fence();
             // glue <= 2 would pin it for ever; an imported clause has to earn that here
@@ -2041,6 +2077,7 @@ DEV void import_shared(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& 
     }
     ls.share_pos = pos;
     if (skipped && w.lane == 0) WK_PTR(MsState, w, L, state)->n_import_skipped += skipped;
+    if (dropped && w.lane == 0) WK_PTR(MsState, w, L, state)->n_imports_dropped_full += dropped;
 }
 
 // A conflict was found by propagate(): learn, backjump, assert (Glucose `search` conflict branch).
@@ -2072,13 +2109,11 @@ DEV bool on_conflict_body(Wk& w, const MsShared& sh, const MsLayout& L, LoopStat
     if (w.status != MS_ST_RUNNING) return false;
     Gp<const int32_t> learnt_buf = WK_PTR(int32_t, w, L, learnt_buf);
     if (ls.proof_buf) {   // DRUP: every learnt clause, in derivation order
-        const uint32_t o = *ls.proof_len;
-        if (o + (uint32_t)lr.n + 1 <= ls.proof_cap) {
+        const uint32_t o = proof_lemma_slot(w, ls, (uint32_t)lr.n + 1);
+        if (o != 0xffffffffu) {
             for (int i = w.lane; i < lr.n; i += MS_WAVE) ls.proof_buf[o + i] = learnt_buf[i];
             if (w.lane == 0) ls.proof_buf[o + lr.n] = -1;
         }
-        wave_fence();
-        if (w.lane == 0) *ls.proof_len = o + (uint32_t)lr.n + 1;
         wave_fence();
     }
 #ifndef MS_SHARE_SMALL
@@ -2205,13 +2240,11 @@ DEV bool vivify_pass(Wk& w, const MsShared& sh, const MsLayout& L, LoopState& ls
         const bool mine = (kept >> w.lane) & 1ull;
         const int rank = popc64(kept & lanemask_lt(w.lane));
         if (ls.proof_buf) {   // DRUP: the shorter clause is a lemma
-            const uint32_t o = *ls.proof_len;
-            if (o + (uint32_t)n_new + 1 <= ls.proof_cap) {
+            const uint32_t o = proof_lemma_slot(w, ls, (uint32_t)n_new + 1);
+            if (o != 0xffffffffu) {
                 if (mine) ls.proof_buf[o + rank] = lit;
                 if (w.lane == 0) ls.proof_buf[o + n_new] = -1;
             }
-            wave_fence();
-            if (w.lane == 0) *ls.proof_len = o + (uint32_t)n_new + 1;
             wave_fence();
         }
         if (n_new == 1) {     // a new level-0 fact; the old clause is satisfied by it
@@ -2272,11 +2305,15 @@ DEV void on_fixpoint_body(Wk& w, const MsShared& sh, const MsLayout& L, LoopStat
     }
     if (ls.conflicts >= ls.next_reduce || w.n_learnts > L.learnt_cap - L.learnt_cap / 8 ||
         w.lc_lits_n > L.learnt_lit_cap - L.learnt_lit_cap / 8) {
+        if (ls.conflicts < ls.next_reduce && w.lane == 0) WK_PTR(MsState, w, L, state)->n_pressure_reduces++;   // the store's doing
         ls.reduce_dbs++;
         ls.next_reduce = ls.conflicts + reduce_first + (u64)reduce_inc * ls.reduce_dbs;
         reduce_db<LV>(w, sh, L, &ls);
     }
-    if (w.pool_top > L.pool_cap - L.pool_cap / 4) rebuild_watches(w, sh, L);  // pool running low: collect holes
+    if (w.pool_top > L.pool_cap - L.pool_cap / 4) {   // pool running low: collect holes (the kernel's decision branch sends a
+        if (w.lane == 0) WK_PTR(MsState, w, L, state)->n_pool_rebuilds++;   // fixpoint here for this alone, too)
+        rebuild_watches(w, sh, L);
+    }
     PROF_MARK(PF_REDUCE);
     if (w.status != MS_ST_RUNNING) return;
     if (ls.share_pool && ls.share_n > ls.share_pos &&
@@ -2376,7 +2413,7 @@ __global__ __launch_bounds__(MS_WAVE, WPS) void ms_search_kernel(MsShared sh, Ms
     ls.n_assumps = st->n_assumps; ls.lbdq = (LdsU32)s_lbdq;
     // DRUP: every worker logs the clauses it learns into its own buffer; the host drains all of them after each slice
     ls.proof_buf = prm.proof_buf ? (Gp<int32_t>)prm.proof_buf + (size_t)wid * prm.proof_cap : nullptr;
-    ls.proof_len = (Gp<uint32_t>)prm.proof_len + wid; ls.proof_cap = prm.proof_cap;
+    ls.proof_len = (Gp<uint32_t>)prm.proof_len + 2 * (size_t)wid; ls.proof_cap = prm.proof_cap;
     ls.share_pool = (Gp<const int4>)prm.share_pool;
     ls.share_n = prm.share_pool ? *(Gp<const unsigned long long>)prm.share_n : 0;
     ls.share_pos = st->share_pos; ls.n_exported = st->n_exported; ls.n_imported = st->n_imported;

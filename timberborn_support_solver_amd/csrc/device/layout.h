@@ -180,6 +180,10 @@ struct MsState {
     // test-hook counters (mi355sat_debug_heuristics): exchanged records passed over by import_pct; imports that
     // share_interval forced above level 0 (a cancel_until(0) in mid-search)
     uint64_t n_import_skipped, n_forced_imports;
+    // test-hook counters (mi355sat_debug_capacities): reductions that store pressure made due (the 7/8 rule, the inline
+    // one of a full store); watch-pool collections because pool_top passed 3/4 of pool_cap; exchanged records passed over
+    // because the learnt store had no room for them even after a reduction
+    uint64_t n_pressure_reduces, n_pool_rebuilds, n_imports_dropped_full;
 };
 
 // Launch parameters of one slice.
@@ -196,7 +200,8 @@ struct MsParams {
     int32_t pad;
     uint32_t reduce_first, reduce_inc;
     int32_t* proof_buf;            // optional DRUP log: proof_cap words per worker; learnt clauses as internal literals, -1 terminated
-    uint32_t* proof_len;           // per worker: words used / wanted since the last drain (overflow: proof_len > proof_cap)
+    uint32_t* proof_len;           // per worker two words since the last drain: lemma words used / wanted from word 0 up (overflow:
+                                   // more than proof_cap), words of deletion lines from the top of the log down
     uint32_t proof_cap, pad2;
     // clause exchange (share_pool == nullptr: off)
     const int32_t* share_pool;     // ring of share_slots records

@@ -442,6 +442,12 @@ struct mi355sat {
     // test hooks: the optional heuristics' counters over the workers of the last solve; their schedule (0 = the defaults)
     mi355sat_heuristics_info heur{};
     uint32_t first_vivify = 0, vivify_every = 0, rephase_every = 0;
+    // test hook (mi355sat_debug_set_capacities): the store sizes of the next cold start of a search (0 = the rule), the
+    // layout the last one got (mi355sat_debug_capacities), and the workers' three store-pressure counters of the last search
+    uint32_t want_learnt_cap = 0, want_learnt_lit_cap = 0, want_pool_slack = 0, want_proof_cap = 0;
+    mi355sat_capacity_info cap_info{};
+    bool cap_info_valid = false;
+    uint64_t cap_events[3] = {0, 0, 0};
     // test hook (mi355sat_debug_keep_simplified): what simplify_formula left at the last cold start, as 0-terminated clauses
     // of DIMACS literals in the caller's variables; [0] the formula the workers get, [1] the kept sides of the eliminations
     bool keep_simplified = false, kept_valid = false;
@@ -787,8 +793,9 @@ void prepare(const mi355sat& s, bool simplify, Prepared& P, bool identity_order 
 
 // ---- slab template -----------------------------------------------------------------
 // learnt_cap / learnt_lit_cap: 0 = the rule below (what a search wants); the proof checker sizes both stores from its proof.
+// pool_slack (test hook, mi355sat_debug_set_capacities): the watch pool is the initial lists plus that many entries; 0 = the rule.
 void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_t script_cap,
-                               std::vector<char>& tmpl, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0) {
+                               std::vector<char>& tmpl, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0, uint32_t pool_slack = 0) {
     const uint32_t nv = P.n_vars, no = (uint32_t)P.cl_hdr.size();
     MsLayout& L = s.L;
     memset(&L, 0, sizeof L);
@@ -819,6 +826,7 @@ void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_c
     // room for a dense rebuild with every learnt slot in use, plus 50% for relocations in between
     uint64_t dense_max = 3 * ((uint64_t)no + L.learnt_cap) + 4 * (uint64_t)nv;   // (rebuild_watches: size + size/2 + 2 per list)
     uint64_t pool_cap = dense_max + dense_max / 2 + (1u << 16);
+    if (pool_slack) pool_cap = pool_need + pool_slack;
     if (pool_cap > 0xfffffff0ull) throw HipErr{"formula too large (watch pool)"};
     L.pool_cap = (uint32_t)pool_cap;
     size_t off = 0;
@@ -905,10 +913,11 @@ void build_layout_and_template(mi355sat& s, const Prepared& P, uint32_t assump_c
 void set_error(mi355sat* s, const std::string& m) { s->err = m; }
 
 void upload_formula(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_t script_cap, uint32_t want_workers,
-                    uint32_t initial_workers = 0, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0, int no_room_code = MI355SAT_ERR_HIP) {
+                    uint32_t initial_workers = 0, uint32_t learnt_cap = 0, uint32_t learnt_lit_cap = 0, int no_room_code = MI355SAT_ERR_HIP,
+                    uint32_t pool_slack = 0) {
     HIPCHK(hipSetDevice(s.device));
     std::vector<char> tmpl;
-    build_layout_and_template(s, P, assump_cap, script_cap, tmpl, learnt_cap, learnt_lit_cap);
+    build_layout_and_template(s, P, assump_cap, script_cap, tmpl, learnt_cap, learnt_lit_cap, pool_slack);
     s.n_vars = P.n_vars;
     s.perm = P.perm;
     s.d_cl_lits.upload(P.cl_lits, s.stream);
@@ -1567,6 +1576,7 @@ void for_each_counter(A& a, B& b, Op op) {
     op(a.slice_cycles, b.slice_cycles); op(a.learnt_total, b.learnt_total); op(a.learnt_lits_total, b.learnt_lits_total);
     op(a.n_vivified, b.n_vivified); op(a.n_viv_lits, b.n_viv_lits); op(a.n_rephase, b.n_rephase);
     op(a.n_import_skipped, b.n_import_skipped); op(a.n_forced_imports, b.n_forced_imports);
+    op(a.n_pressure_reduces, b.n_pressure_reduces); op(a.n_pool_rebuilds, b.n_pool_rebuilds); op(a.n_imports_dropped_full, b.n_imports_dropped_full);
     for (int i = 0; i < 16; i++) op(a.prof[i], b.prof[i]);
 }
 
@@ -1589,6 +1599,7 @@ void accumulate_stats(mi355sat& s, const std::vector<MsState>& sts, uint64_t bcp
     s.heur = mi355sat_heuristics_info{};
     s.heur.n_vivified = t.n_vivified; s.heur.n_viv_lits = t.n_viv_lits; s.heur.n_rephase = t.n_rephase;
     s.heur.import_skipped = t.n_import_skipped; s.heur.forced_imports = t.n_forced_imports;
+    s.cap_events[0] = t.n_pressure_reduces; s.cap_events[1] = t.n_pool_rebuilds; s.cap_events[2] = t.n_imports_dropped_full;
     const uint64_t* prof = t.prof;
     const uint64_t cyc = t.slice_cycles;
     if (prof[0] && s.opts.verbose) {
@@ -1755,26 +1766,29 @@ void proof_open(mi355sat& s) {
 }
 void proof_drain(mi355sat& s) {
     if (!s.proof_file || !s.d_proof_len.p) return;
-    const uint32_t W = (uint32_t)s.d_proof_len.n;
-    std::vector<uint32_t> len(W);
-    HIPCHK(hipMemcpy(len.data(), s.d_proof_len.p, sizeof(uint32_t) * W, hipMemcpyDeviceToHost));
+    const uint32_t W = (uint32_t)(s.d_proof_len.n / 2);     // per worker: lemma words from word 0 up, deletion words from the top down
+    std::vector<uint32_t> len(2 * (size_t)W);
+    HIPCHK(hipMemcpy(len.data(), s.d_proof_len.p, sizeof(uint32_t) * 2 * W, hipMemcpyDeviceToHost));
     std::vector<uint32_t> inv(s.perm.size());
     for (uint32_t e = 0; e < s.perm.size(); e++) inv[s.perm[e]] = e;
     std::vector<int32_t> buf;
     bool any = false;
     for (uint32_t w = 0; w < W; w++) {
-        if (!len[w]) continue;
+        const uint32_t n_lem = len[2 * w], n_del = len[2 * w + 1];
+        if (!n_lem && !n_del) continue;
         any = true;
-        if (len[w] > s.proof_cap) throw HipErr{"proof buffer overflow (a worker learnt more in one slice than its log holds)"};
-        buf.resize(len[w]);
-        HIPCHK(hipMemcpy(buf.data(), s.d_proof.p + (size_t)w * s.proof_cap, sizeof(int32_t) * len[w], hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < len[w]; i++) {
+        if (n_lem > s.proof_cap || n_del > s.proof_cap - n_lem)
+            throw HipErr{"proof buffer overflow (a worker learnt more in one slice than its log holds)", MI355SAT_ERR_OOM};
+        buf.resize((size_t)n_lem + n_del);     // the lemmas, then the deletion lines
+        if (n_lem) HIPCHK(hipMemcpy(buf.data(), s.d_proof.p + (size_t)w * s.proof_cap, sizeof(int32_t) * n_lem, hipMemcpyDeviceToHost));
+        if (n_del) HIPCHK(hipMemcpy(buf.data() + n_lem, s.d_proof.p + (size_t)w * s.proof_cap + (s.proof_cap - n_del), sizeof(int32_t) * n_del, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < buf.size(); i++) {
             if (buf[i] == -2) fputs("d ", s.proof_file);       // deletion line
             else if (buf[i] < 0) fputs("0\n", s.proof_file);
             else fprintf(s.proof_file, "%d ", (buf[i] & 1) ? -((int)inv[buf[i] >> 1] + 1) : ((int)inv[buf[i] >> 1] + 1));
         }
     }
-    if (any) { HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * W, s.stream)); HIPCHK(hipStreamSynchronize(s.stream)); }
+    if (any) { HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * W, s.stream)); HIPCHK(hipStreamSynchronize(s.stream)); }
 }
 // An UNSAT answer ends the proof with the clause of the negated core: under assumptions, what the formula implies about
 // them; without any (or when the formula itself is refuted), the empty clause.
@@ -1971,7 +1985,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     if (keep) max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)keep->size());
     const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps + (sw.keep_warm ? 256u : 0u);
     const uint32_t initial = (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) ? std::max(256u, n_instances) / n_instances * n_instances : 0;
-    upload_formula(s, P, assump_cap, 0, want, initial);
+    upload_formula(s, P, assump_cap, 0, want, initial, s.want_learnt_cap, s.want_learnt_lit_cap, MI355SAT_ERR_HIP, s.want_pool_slack);
     if (s.n_workers < n_instances) throw HipErr{"not enough device memory for one worker per instance"};
     s.n_workers = s.n_workers / n_instances * n_instances;
     s.n_alloc = std::min(s.n_alloc, s.n_workers);
@@ -1979,10 +1993,17 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         // deletion lines of one clause-database reduction, which may drop half of a full learnt store at once (lemmas that do
         // not fit fail the solve - the proof would be wrong; deletion lines that do not fit are dropped - they are optional)
         s.proof_cap = (uint32_t)std::min<uint64_t>(1u << 23, (1u << 20) + s.L.learnt_lit_cap / 2 + 2ull * s.L.learnt_cap);
+        if (s.want_proof_cap) s.proof_cap = s.want_proof_cap;
         s.d_proof.alloc((size_t)s.n_workers * s.proof_cap);
-        s.d_proof_len.alloc(s.n_workers);
-        HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * s.n_workers, s.stream));
+        s.d_proof_len.alloc(2 * (size_t)s.n_workers);
+        HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * s.n_workers, s.stream));
     }
+    s.cap_info = mi355sat_capacity_info{};
+    s.cap_info.learnt_cap = s.L.learnt_cap; s.cap_info.learnt_lit_cap = s.L.learnt_lit_cap; s.cap_info.pool_cap = s.L.pool_cap;
+    s.cap_info.pool_initial = (uint32_t)s.pool_init; s.cap_info.proof_cap = s.proof_cap; s.cap_info.assump_cap = s.L.assump_cap;
+    s.cap_info.vm_cap = s.L.vm_cap;
+    s.cap_info_valid = true;
+    s.cap_events[0] = s.cap_events[1] = s.cap_events[2] = 0;
     reset_workers(s);
     customize(s, &a_int, &a_off, nullptr, nullptr, n_instances, sw.split ? (int32_t)n_instances : -1);
     s.ph.dev_fixed.assign(P.n_vars, 0);
@@ -3246,6 +3267,27 @@ int mi355sat_debug_incremental(const mi355sat* s, mi355sat_incremental_info* out
 int mi355sat_debug_heuristics(const mi355sat* s, mi355sat_heuristics_info* out) {
     if (!s || !out) return MI355SAT_ERR_ARG;
     *out = s->heur;
+    return 0;
+}
+
+int mi355sat_debug_set_capacities(mi355sat* s, uint32_t learnt_cap, uint32_t learnt_lit_cap, uint32_t pool_slack, uint32_t proof_cap) {
+    if (!s) return MI355SAT_ERR_ARG;
+    // floors: conflict-clause minimisation keeps two node lists of learnt_cap / 2 entries in `remap`; add_learnt wants a
+    // clause plus 8 words; a proof log holds at least one short lemma.  Ceilings: the rule's own maxima.
+    if ((learnt_cap && (learnt_cap < 4 || learnt_cap > (1u << 17))) || (learnt_lit_cap && (learnt_lit_cap < 64 || learnt_lit_cap > (2u << 20))) ||
+        pool_slack > (1u << 30) || (proof_cap && (proof_cap < 8 || proof_cap > (1u << 23)))) {
+        s->err = "debug_set_capacities: a capacity outside its range";
+        return MI355SAT_ERR_ARG;
+    }
+    s->want_learnt_cap = learnt_cap; s->want_learnt_lit_cap = learnt_lit_cap; s->want_pool_slack = pool_slack; s->want_proof_cap = proof_cap;
+    return 0;
+}
+
+int mi355sat_debug_capacities(const mi355sat* s, mi355sat_capacity_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    if (!s->cap_info_valid) return MI355SAT_ERR_STATE;
+    *out = s->cap_info;
+    out->pressure_reduces = s->cap_events[0]; out->pool_rebuilds = s->cap_events[1]; out->imports_dropped_full = s->cap_events[2];
     return 0;
 }
 

@@ -86,6 +86,15 @@ class Mi355SatHeuristicsInfo(ctypes.Structure):   # mi355sat_heuristics_info (te
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Mi355SatCapacityInfo(ctypes.Structure):   # mi355sat_capacity_info (test hook)
+    _fields_ = [(n, ctypes.c_uint32) for n in ("learnt_cap", "learnt_lit_cap", "pool_cap", "pool_initial", "proof_cap", "assump_cap",
+                                               "vm_cap", "pad")] + \
+               [(n, ctypes.c_uint64) for n in ("pressure_reduces", "pool_rebuilds", "imports_dropped_full")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
 class Mi355SatPhaseInfo(ctypes.Structure):   # mi355sat_phase_info (test hook)
     _fields_ = [(n, ctypes.c_uint64) for n in ("hinted", "applied_cold", "applied_warm", "launches", "mapped",
                                                "dropped_eliminated", "dropped_fixed")]
@@ -194,6 +203,8 @@ def _bind(L):
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
     L.mi355sat_debug_set_schedule.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+    L.mi355sat_debug_set_capacities.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+    L.mi355sat_debug_capacities.argtypes = [vp, ctypes.POINTER(Mi355SatCapacityInfo)]
     L.mi355sat_phase.argtypes = [vp, ctypes.c_int32]
     L.mi355sat_unphase.argtypes = [vp, ctypes.c_int32]
     L.mi355sat_set_phases.argtypes = [vp, vp, ctypes.c_uint64]
@@ -569,6 +580,19 @@ class Mi355Sat:
         """Test hook: conflicts of one worker before its first vivification pass, between passes, and before its first
         rephasing (0 = the defaults 1500 / 400 / 2000), from the next solve on."""
         self._check(self._L.mi355sat_debug_set_schedule(self._h, first_vivify, vivify_every, rephase_every), "debug_set_schedule")
+
+    def debug_set_capacities(self, learnt_cap=0, learnt_lit_cap=0, pool_slack=0, proof_cap=0):
+        """Test hook: the sizes of a worker's stores from the next cold start of a search on (0 = the sizing rule): learnt-clause
+        slots, learnt literal words, watch-pool entries beyond the initial lists, proof-log words."""
+        self._check(self._L.mi355sat_debug_set_capacities(self._h, learnt_cap, learnt_lit_cap, pool_slack, proof_cap), "debug_set_capacities")
+
+    def debug_capacities(self):
+        """Test hook: the store sizes of the last cold start, and - summed over the workers of the last search - the
+        reductions that store pressure made due, the watch-pool collections of a pool three quarters full, the exchanged
+        records passed over for want of room."""
+        info = Mi355SatCapacityInfo()
+        self._check(self._L.mi355sat_debug_capacities(self._h, ctypes.byref(info)), "debug_capacities")
+        return info.as_dict()
 
     def lit_val(self, lit):
         return self._L.mi355sat_val(self._h, int(lit))
