@@ -588,6 +588,47 @@ int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* targ
  * (launches of about 20 ms). */
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch);
 
+
+/* Trim a DRUP proof while it is checked: which of the caller's clauses and which lemmas the derivation of the target
+ * rests on, and - with MI355SAT_TRIM_HINTS - an LRAT file that a checker without watch lists, search or GPU verifies
+ * (DESIGN.md 4).  The check is mi355sat_check_proof's, in a tracing build of the same kernel: `check` holds exactly what
+ * mi355sat_check_proof reports for the same inputs, and argument errors, the interrupt, "takes the device over", the
+ * IPASIR state, the phase hints and n_sat / n_unsat / n_terminated behave as there.  Whenever a check ends in a
+ * conflict the worker walks its trail back from it and writes the clauses it passes to a log of its own; the host
+ * drains the logs after every launch, maps them to the caller's clauses and, once the proof is found valid, reaches
+ * backwards from the target.
+ * Indices: caller clause i is the i-th clause the handle was given, 0-based (mi355sat_add_cnf order, each clause closed by
+ * mi355sat_add(0)); a clause given twice is named by its first index.  Lemma j is the j-th lemma line, 0-based.  LRAT
+ * ids: clause i has id i + 1, lemma j has n_clauses + 1 + j, the target n_clauses + 1 + n_lemmas; a line is
+ * "id literals 0 hints 0"; the needed lemmas in order, then the target; no deletion lines.  A tautological target rests
+ * on nothing: empty core, no lemma, no LRAT line.  When the caller's clauses hold an empty clause or two contradictory
+ * units, the core is that clause or pair and the file is the target's line alone.
+ * The verdict, first_failed and refuted_at are functions of formula, proof and target alone.  WHICH clauses end up in
+ * the core is not: unit propagation picks one of several clauses that give the same literal at the same moment, so the
+ * sets may differ with `segments` and from run to run.  Every one of them passes the checks named above.
+ * The result stays on the handle until the next mi355sat_trim_proof / mi355sat_check_proof, a clause added, a sweep begun
+ * or mi355sat_free; without one - also after a trim whose verdict was not valid == 1 or that was interrupted - the four
+ * calls below return MI355SAT_ERR_STATE.  Both index calls: out NULL sizes (*n), a cap too small is MI355SAT_ERR_ARG. */
+#define MI355SAT_TRIM_HINTS 1u          /* keep the hints: needed for mi355sat_trim_write_lrat */
+typedef struct mi355sat_trim_info {
+    mi355sat_proof_info check;          /* exactly what mi355sat_check_proof reports for the same inputs */
+    uint64_t core_clauses, lemmas_needed;      /* sizes of the two sets (0 unless check.valid == 1) */
+    uint64_t dep_records;               /* records drained from the device */
+    uint64_t log_drains;                /* launches after which a region was non-empty */
+    uint64_t log_words_per_worker;
+} mi355sat_trim_info;
+int mi355sat_trim_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
+                        uint32_t segments, uint32_t flags, mi355sat_trim_info* out);
+int mi355sat_trim_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target,
+                             uint32_t segments, uint32_t flags, mi355sat_trim_info* out);
+int mi355sat_trim_core(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n);     /* caller clause indices, ascending */
+int mi355sat_trim_lemmas(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n);   /* lemma indices, ascending */
+int mi355sat_trim_write_drup(mi355sat* s, const char* path);   /* the needed lemmas in order, then the target */
+int mi355sat_trim_write_lrat(mi355sat* s, const char* path);   /* MI355SAT_ERR_STATE without MI355SAT_TRIM_HINTS */
+/* Test hook: words per worker of the dependency log; 0 = the rule (2^18, less for large fleets); never below two items of
+ * the largest size (8 * (n_vars + 3) words): a worker ends its launch when less than that is free. */
+int mi355sat_debug_trim_log(mi355sat* s, uint32_t words_per_worker);
+
 #ifdef __cplusplus
 }
 #endif

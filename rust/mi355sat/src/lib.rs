@@ -64,6 +64,19 @@ pub struct ProofInfo {
     pub launches: u64, pub seconds: f64, pub kernel_seconds: f64,
 }
 
+/// Mirror of `mi355sat_trim_info`: what `trim_proof` found.
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct TrimInfo {
+    /// exactly what `check_proof` reports for the same inputs
+    pub check: ProofInfo,
+    /// sizes of the clause core and of the set of needed lemmas (0 unless `check.valid == 1`)
+    pub core_clauses: u64, pub lemmas_needed: u64,
+    pub dep_records: u64, pub log_drains: u64, pub log_words_per_worker: u64,
+}
+/// `MI355SAT_TRIM_HINTS`: keep what `write_lrat` needs.
+pub const TRIM_HINTS: u32 = 1;
+
 extern "C" {
     fn mi355sat_new(opts: *const Opts) -> *mut c_void;
     fn mi355sat_free(s: *mut c_void);
@@ -79,6 +92,11 @@ extern "C" {
     fn mi355sat_minimize_core(s: *mut c_void, conflict_budget: i64, out: *mut CoreMinInfo) -> c_int;
     fn mi355sat_check_proof(s: *mut c_void, proof: *const i32, n_words: u64, target: *const i32, n_target: u64, segments: u32,
                             out: *mut ProofInfo) -> c_int;
+    fn mi355sat_trim_proof(s: *mut c_void, proof: *const i32, n_words: u64, target: *const i32, n_target: u64, segments: u32,
+                           flags: u32, out: *mut TrimInfo) -> c_int;
+    fn mi355sat_trim_core(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
+    fn mi355sat_trim_lemmas(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
+    fn mi355sat_trim_write_lrat(s: *mut c_void, path: *const c_char) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
     fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
@@ -160,6 +178,36 @@ impl Mi355Sat {
         };
         if rc < 0 { return Err(self.err()); }
         Ok(info)
+    }
+    /// Trimmed certificate (`mi355sat_trim_proof`): `check_proof` in the tracing build of the checker.  Where
+    /// `check.valid == 1`, `trim_core` / `trim_lemmas` name the clauses of this handle (0-based, in the order they were
+    /// added) and the lemmas the derivation of `target` rests on; with `hints`, `write_lrat` writes an LRAT file a checker
+    /// without search verifies.  Which clauses make the core may differ with `segments` and from run to run.
+    pub fn trim_proof(&mut self, proof: &[i32], target: &[i32], segments: u32, hints: bool) -> anyhow::Result<TrimInfo> {
+        let mut info = TrimInfo::default();
+        let rc = unsafe {
+            mi355sat_trim_proof(self.h, proof.as_ptr(), proof.len() as u64, target.as_ptr(), target.len() as u64, segments,
+                                if hints { TRIM_HINTS } else { 0 }, &mut info)
+        };
+        if rc < 0 { return Err(self.err()); }
+        Ok(info)
+    }
+    fn indices(&mut self, get: unsafe extern "C" fn(*mut c_void, *mut u64, u64, *mut u64) -> c_int) -> anyhow::Result<Vec<u64>> {
+        let mut n = 0u64;
+        if unsafe { get(self.h, std::ptr::null_mut(), 0, &mut n) } < 0 { return Err(self.err()); }
+        let mut out = vec![0u64; n as usize];
+        if unsafe { get(self.h, out.as_mut_ptr(), n, &mut n) } < 0 { return Err(self.err()); }
+        Ok(out)
+    }
+    /// The clause core of the last valid `trim_proof`, ascending; an error (`MI355SAT_ERR_STATE`) in any other state.
+    pub fn trim_core(&mut self) -> anyhow::Result<Vec<u64>> { self.indices(mi355sat_trim_core) }
+    /// The lemmas it needs, ascending.
+    pub fn trim_lemmas(&mut self) -> anyhow::Result<Vec<u64>> { self.indices(mi355sat_trim_lemmas) }
+    /// The needed lemmas and the target as LRAT (clause i has id i + 1, lemma j has n_clauses + 1 + j).
+    pub fn write_lrat(&mut self, path: &std::path::Path) -> anyhow::Result<()> {
+        let p = std::ffi::CString::new(path.to_string_lossy().as_bytes())?;
+        if unsafe { mi355sat_trim_write_lrat(self.h, p.as_ptr()) } < 0 { return Err(self.err()); }
+        Ok(())
     }
     fn err(&self) -> anyhow::Error {
         let m = unsafe { std::ffi::CStr::from_ptr(mi355sat_last_error(self.h)) };

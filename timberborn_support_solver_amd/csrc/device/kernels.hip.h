@@ -2910,6 +2910,206 @@ __global__ __launch_bounds__(MS_WAVE) void ms_attach_kernel(MsShared sh, MsLayou
     wk_store<false>(w, sh, L, 0);
 }
 
+// ---- what a RUP check rests on (the tracing build of ms_rup_kernel, mi355sat_trim_proof) ---
+// Three marks per variable: LDS builds keep them in the bitmaps no analysis uses in this kernel (lseen, lfail, lq), the
+// others in the three low bits of MsVarRec.seen.  SEEN: the walk's marks.  ASSUMED / CAND: the level-0 variables of the
+// lemma under check whose literal there is FALSE / TRUE - set before the check, cleared after it.
+enum { TR_SEEN = 1, TR_ASSUMED = 2, TR_CAND = 4 };
+template <bool LV>
+DEV LdsU32 tr_map(const Wk& w, int bit) { return bit == TR_SEEN ? w.lseen : (bit == TR_ASSUMED ? w.lfail : w.lq); }
+template <bool LV>
+DEV bool tr_get(const Wk& w, const MsLayout& L, int v, int bit) {
+    if (LV) return (tr_map<LV>(w, bit)[v >> 5] >> (v & 31)) & 1u;
+    return (VREC[v].seen & bit) != 0;
+}
+template <bool LV>
+DEV void tr_set(const Wk& w, const MsLayout& L, int v, int bit) {
+    if (LV) lds_or(&tr_map<LV>(w, bit)[v >> 5], 1u << (v & 31));
+    else VREC[v].seen = (uint8_t)(VREC[v].seen | bit);
+}
+template <bool LV>
+DEV void tr_clr(const Wk& w, const MsLayout& L, int v, int bit) {
+    if (LV) lds_and(&tr_map<LV>(w, bit)[v >> 5], ~(1u << (v & 31)));
+    else VREC[v].seen = (uint8_t)(VREC[v].seen & ~bit);
+}
+template <bool LV>
+DEV void tr_sync() {
+    wave_fence();
+    if (LV) lds_fence();
+}
+// ASSUMED / CAND of the lemma cl[b .. e) at level 0 (set = false: take them back).  Returns whether any variable got one.
+template <bool LV>
+DEV bool tr_lemma_marks(const Wk& w, const MsShared& sh, const MsLayout& L, Gp<const int32_t> cl, uint32_t b, uint32_t e, bool set) {
+    bool any = false;
+    for (uint32_t k0 = b; k0 < e; k0 += MS_WAVE) {
+        const uint32_t k = k0 + (uint32_t)w.lane;
+        const bool in = k < e;
+        const int lit = in ? cl[k] : 0;
+        const bool ok = in && (uint32_t)lit < 2u * sh.n_vars;
+        if (!set) {
+            if (ok) { tr_clr<LV>(w, L, lit >> 1, TR_ASSUMED); tr_clr<LV>(w, L, lit >> 1, TR_CAND); }
+            continue;
+        }
+        const int v = ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_UNDEF;
+        if (v == MS_VAL_FALSE) tr_set<LV>(w, L, lit >> 1, TR_ASSUMED);
+        if (v == MS_VAL_TRUE) tr_set<LV>(w, L, lit >> 1, TR_CAND);
+        any = any || ballot(v != MS_VAL_UNDEF) != 0;
+    }
+    tr_sync<LV>();
+    return any;
+}
+
+// The walk back from the end of a check, ms_final_kernel's shape: from the clause that ended it - the conflict propagate
+// left in w.confl_* (from = 0), the reason of the lemma's lowest TRUE literal (from = 1: every other literal the lemma has
+// at level 0 then stands above that reason's cone or is ASSUMED), or lemma `from_lemma` found without a free literal
+// (from = 2) - down the trail to position 0, level 0 included, 64 positions per round.  A marked literal that the negated
+// lemma does not assume emits its reason as a record and marks the reason's variables; a lemma - as a reason or as the
+// origin of a level-0 fact - is expanded from the proof buffer (cl / co), the full literal list: the store's copy lacks the
+// literals that were FALSE at level 0 when it was attached, and their derivations belong to the cone.  The marks of a
+// window of 64 positions are taken back when the walk leaves it.  Lemmas >= lim and clause
+// references outside the stores are MS_ST_ERR_INTERNAL.  The item goes to the worker's log region at `used` (the caller
+// has made sure a whole item fits).
+template <bool LV>
+DEV void rup_trace(Wk& w, const MsShared& sh, const MsLayout& L, const MsTrace& tr, uint32_t wid, uint32_t& used, uint32_t item,
+                   uint32_t lim, int from, uint32_t from_lemma, Gp<const int32_t> cl, Gp<const uint32_t> co) {
+    Gp<const int32_t> trail = WKA(int32_t, trail);
+    Gp<const MsVarRec> vrec = WKA(MsVarRec, vrec);
+    Gp<const uint32_t> slot_lemma = WKA(uint32_t, remap);
+    Gp<int4> out = (Gp<int4>)((Gp<uint32_t>)tr.log + (size_t)wid * tr.words + used);    // [0] the header
+    const uint32_t max_rec = sh.n_vars + 2;
+    uint32_t n_rec = 0;
+    bool bad = false;
+    auto mark = [&](int q, int own) {
+        if ((uint32_t)q < 2u * sh.n_vars && (q >> 1) != own) tr_set<LV>(w, L, q >> 1, TR_SEEN);
+    };
+    // all lanes: the variables of a clause's literals base[s0 .. s0 + n), 64 per round
+    auto mark_range = [&](Gp<const int32_t> base, uint32_t s0, uint32_t n, int own) {
+        for (uint32_t k0 = 0; k0 < n; k0 += MS_WAVE) {
+            const uint32_t k = k0 + (uint32_t)w.lane;
+            if (k < n) mark(base[s0 + k], own);
+        }
+    };
+    auto mark_lemma = [&](uint32_t jl, int own) {
+        const uint32_t s0 = (uint32_t)uni((int)co[jl]), s1 = (uint32_t)uni((int)co[jl + 1]);
+        mark_range(cl, s0, s1 - s0, own);
+    };
+    auto emit = [&](bool want, int tag, int pos, int a, int b, int c) {    // all lanes call
+        const u64 em = ballot(want);
+        if (n_rec + (uint32_t)popc64(em) > max_rec) { bad = true; return; }
+        if (want) out[1 + n_rec + (uint32_t)popc64(em & lanemask_lt(w.lane))] = make_int4((tag << 28) | pos, a, b, c);
+        n_rec += (uint32_t)popc64(em);
+    };
+    tr_sync<LV>();
+    int top = w.trail_n;
+    if (from == 1) {            // the lowest TRUE literal of the lemma: its reason is falsified under the negated lemma
+        const int lim0 = w.n_levels > 0 ? uni(WK_PTR(int32_t, w, L, trail_lim)[0]) : w.trail_n;
+        top = -1;
+        for (int p0 = 0; p0 < lim0 && top < 0; p0 += MS_WAVE) {
+            const int pos = p0 + w.lane;
+            const int v = pos < lim0 ? trail[pos] >> 1 : -1;
+            const u64 bm = ballot(v >= 0 && (uint32_t)v < sh.n_vars && tr_get<LV>(w, L, v, TR_CAND));
+            if (bm) top = p0 + first_lane(bm) + 1;
+        }
+        if (top < 0) bad = true;
+        else if (w.lane == 0) tr_set<LV>(w, L, trail[top - 1] >> 1, TR_SEEN);
+    } else if (from == 2) {
+        if (from_lemma >= lim) bad = true;
+        else {
+            mark_lemma(from_lemma, -1);
+            emit(w.lane == 0, MS_TR_LEMMA, top, (int)from_lemma, 0, -1);
+        }
+    } else if (w.confl_kind == 1) {
+        const uint32_t cref = (uint32_t)w.confl_cref;
+        if (cref < sh.n_orig) {
+            mark_range((Gp<const int32_t>)sh.cl_lits, (uint32_t)w.confl_b, (uint32_t)w.confl_c, -1);
+            emit(w.lane == 0, MS_TR_LONG, top, (int)cref, 0, -1);
+        } else if (cref - sh.n_orig < w.n_learnts) {
+            const uint32_t jl = (uint32_t)uni((int)slot_lemma[cref - sh.n_orig]);
+            if (jl >= lim) bad = true;
+            else {
+                mark_lemma(jl, -1);
+                emit(w.lane == 0, MS_TR_LEMMA, top, (int)jl, 0, -1);
+            }
+        } else bad = true;
+    } else if (w.confl_kind == 2 || w.confl_kind == 3) {
+        if (w.lane == 0) {
+            mark(w.confl_a, -1);
+            mark(w.confl_b, -1);
+            if (w.confl_kind == 3) mark(w.confl_c, -1);
+        }
+        emit(w.lane == 0, w.confl_kind == 2 ? MS_TR_BIN : MS_TR_TERN, top, w.confl_a, w.confl_b, w.confl_kind == 3 ? w.confl_c : 0);
+    } else bad = true;
+    for (int hi = top - 1; !bad && hi >= 0; hi -= MS_WAVE) {
+        const int pos = hi - w.lane;
+        const bool in = pos >= 0;
+        const int lit = in ? trail[pos] : 0;
+        const int v = lit >> 1;
+        bool done = false, err = in && (uint32_t)v >= sh.n_vars;
+        while (!bad) {
+            tr_sync<LV>();      // this round's marks are seen by the next
+            const bool mine = in && !err && !done && tr_get<LV>(w, L, v, TR_SEEN);
+            if (ballot(mine) == 0) break;
+            int tag = 0, a = 0, b = 0, c = lit;
+            uint32_t start = 0, size = 0;
+            bool wide = false;           // the clause's variables are marked by the whole wave, below
+            if (mine) {
+                done = true;
+                if (!tr_get<LV>(w, L, v, TR_ASSUMED)) {
+                    const MsVarRec rec = vrec[v];
+                    const int r = rec.reason;
+                    if (r == MS_REASON_NONE) {
+                        if (rec.level == 0) {                       // a fact nobody derived: a unit clause, or a lemma that was unit
+                            if (rec.start == 0) { tag = MS_TR_UNIT; a = lit; }
+                            else { tag = MS_TR_UNIT_LEMMA; a = (int)(rec.start - 1); wide = true; }
+                        }
+                    } else if (MS_IS_TERN_REASON(r)) {
+                        const int e = MS_TERN_REASON_ENTRY(r);
+                        const ms_int2 tp = ((Gp<const ms_int2>)sh.tern_pairs)[e];
+                        tag = MS_TR_TERN;
+                        a = lit; b = ((Gp<const int32_t>)sh.tern_owner)[e] ^ 1; c = tp.x == lit ? tp.y : tp.x;
+                        if (tp.x != lit && tp.y != lit) err = true;
+                    } else if (MS_IS_BIN_REASON(r)) {
+                        tag = MS_TR_BIN;
+                        a = lit; b = MS_BIN_REASON_LIT(r); c = 0;
+                    } else if ((uint32_t)r < sh.n_orig) {
+                        tag = MS_TR_LONG;
+                        a = r; start = rec.start; size = rec.size; wide = true;
+                    } else if ((uint32_t)r - sh.n_orig < w.n_learnts) {
+                        tag = MS_TR_LEMMA;
+                        a = (int)slot_lemma[(uint32_t)r - sh.n_orig]; wide = true;
+                    } else err = true;
+                    if ((tag == MS_TR_LEMMA || tag == MS_TR_UNIT_LEMMA) && (uint32_t)a >= lim) err = true;
+                }
+            }
+            if (mine && !err && tag == MS_TR_TERN) { mark(a, v); mark(b, v); mark(c, v); }
+            if (mine && !err && tag == MS_TR_BIN) mark(b, v);
+            emit(mine && !err && tag != 0, tag, pos, a, b, c);
+            for (u64 bm = ballot(mine && !err && wide); bm != 0 && !bad; bm &= bm - 1) {
+                const int fb = first_lane(bm);
+                const int t = bcast(tag, fb), idx = bcast(a, fb), own = bcast(v, fb);
+                if (t == MS_TR_LONG) {
+                    uint32_t n = (uint32_t)bcast((int)size, fb), s0 = (uint32_t)bcast((int)start, fb);
+                    if (n == 0) {     // (a clause too long for the record's 16 bits)
+                        const MsClauseRec h = WKA(MsClauseRec, wl)[idx];
+                        n = (uint32_t)uni((int)h.size);
+                        s0 = (uint32_t)uni((int)h.start);
+                    }
+                    mark_range((Gp<const int32_t>)sh.cl_lits, s0, n, own);
+                } else mark_lemma((uint32_t)idx, own);
+            }
+            if (ballot(err) != 0) bad = true;
+        }
+        // a clause marks only variables below the literal it implied: this window's marks are final, and taken back
+        tr_sync<LV>();
+        if (done) tr_clr<LV>(w, L, v, TR_SEEN);
+        if (ballot(err) != 0) bad = true;
+    }
+    tr_sync<LV>();
+    if (bad) { w.status = MS_ST_ERR_INTERNAL; return; }
+    if (w.lane == 0) out[0] = make_int4((int)item, (int)n_rec, 0, 0);
+    used += MS_TR_REC * (1 + n_rec);
+}
+
 // ---- forward RUP check of a clausal proof (mi355sat_check_proof) -------------------------
 // Lemma i of a DRUP proof must follow from the formula and the lemmas before it by unit propagation alone: assume the
 // negation of its literals, propagate, expect a conflict - this kernel's hot loop, once per lemma, and the checks of
@@ -2933,10 +3133,16 @@ __global__ __launch_bounds__(MS_WAVE) void ms_attach_kernel(MsShared sh, MsLayou
 // is done: MS_ST_SAT (through its segment) or MS_ST_UNSAT (database refuted).  mins[0] = first_failed, mins[1] =
 // refuted_at, both kept as their complements (a minimum is then one atomicMax, and a zeroed word means "none"): the only
 // words workers share, one atomic by one lane on the rare path.
-template <bool LV>
+// TRACE (mi355sat_trim_proof): the same check, and whenever one ends RUP - or the database falls at level 0 - rup_trace
+// writes what it rested on to the worker's region of the dependency log (layout.h, MsTrace) before the level is taken
+// back.  Two things are remembered for it: the lemma a learnt slot holds (the slab's `remap` array, idle in this kernel),
+// and the lemma behind a level-0 fact that was attached as a unit (j + 1 in the start word of its variable record; 0 = a
+// unit clause of the caller).  A launch also ends when the region has less room left than two items of the largest size
+// (a check and the refutation its attach may find); the host drains the regions after every launch.
+template <bool LV, bool TRACE = false>
 __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L, char* slabs, MsParams prm, const int32_t* lits,
                                                         const uint32_t* offs, const uint8_t* skip, uint32_t n_items,
-                                                        unsigned long long* mins) {
+                                                        unsigned long long* mins, MsTrace tr) {
     __shared__ int32_t s_ring[MS_LDS_RING];
     __shared__ uint32_t s_claim[MS_CLAIM_SLOTS];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[4 * MS_MAX_GROUPS < 64 ? 64 : 4 * MS_MAX_GROUPS];
@@ -2962,7 +3168,10 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
     wk_uniformize(w);
     if (w.status != MS_ST_RUNNING) return;        // done in an earlier launch: nothing was changed, nothing to store
     if (LV) { level_zero_rebuild(w, sh, L); cur_level_rebuild(w, sh, L); }
+    if (LV && TRACE)       // the three mark bitmaps: lseen, lfail (behind lcur and lzero), lq
+        for (uint32_t i = (uint32_t)w.lane; i < ((sh.n_vars + 31) >> 5); i += MS_WAVE) { w.lseen[i] = 0; w.lfail[i] = 0; w.lq[i] = 0; }
     lds_fence();
+    uint32_t log_used = TRACE ? (uint32_t)uni((int)((Gp<const uint32_t>)tr.used)[wid]) : 0u;
     const u64 t0 = __builtin_readcyclecounter();
     const u64 tick0 = __builtin_amdgcn_s_memrealtime();
     Gp<int32_t> cur = WK_PTR(int32_t, w, L, script);
@@ -2980,6 +3189,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
     };
     for (; j < b && budget > 0 && w.status == MS_ST_RUNNING; j++, budget--) {
         if (prm.slice_ticks && __builtin_amdgcn_s_memrealtime() - tick0 >= prm.slice_ticks) break;
+        if (TRACE && (u64)tr.words - log_used < 2 * MS_TR_ITEM_WORDS(sh.n_vars)) break;     // the host drains the log
         // pool running low: collect the holes that grown lists left behind (the search's rule, on_fixpoint_body)
         if (w.pool_top > L.pool_cap - L.pool_cap / 4) {
             rebuild_watches(w, sh, L);
@@ -2991,6 +3201,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             if (propagate<LV>(w, sh, L)) {            // the level-0 queue
                 note_min(1, j);
                 w.status = MS_ST_UNSAT;
+                if (TRACE) rup_trace<LV>(w, sh, L, tr, wid, log_used, j | MS_TR_REFUTED, j, 0, 0, cl, co);
                 break;
             }
             if (w.status != MS_ST_RUNNING) break;
@@ -2998,6 +3209,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
         if (skipped) continue;
         if (j >= a) {
             n_checked++;
+            const bool premarks = TRACE && tr_lemma_marks<LV>(w, sh, L, cl, lb, le, true);
             new_decision_level<LV>(w, sh, L);
             bool rup = false, bad = false;
             for (uint32_t k0 = lb; k0 < le && !rup && !bad; k0 += MS_WAVE) {
@@ -3016,8 +3228,10 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             }
             if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
             const bool confl = rup || propagate<LV>(w, sh, L);
+            if (TRACE && confl && w.status == MS_ST_RUNNING) rup_trace<LV>(w, sh, L, tr, wid, log_used, j, j, rup ? 1 : 0, 0, cl, co);
             cancel_until<LV>(w, sh, L, 0);
             w.confl_kind = 0;
+            if (premarks) tr_lemma_marks<LV>(w, sh, L, cl, lb, le, false);
             if (w.status != MS_ST_RUNNING) break;
             if (!confl) note_min(0, j);
         }
@@ -3030,10 +3244,11 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
         if (cnt == 0) {                               // falsified at level 0: refuted from the next lemma on
             note_min(1, j + 1);
             w.status = MS_ST_UNSAT;
+            if (TRACE) rup_trace<LV>(w, sh, L, tr, wid, log_used, (j + 1) | MS_TR_REFUTED, j + 1, 2, j, cl, co);
             j++;
             break;
         }
-        if (cnt == 1) { enqueue_uniform<LV>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE); continue; }
+        if (cnt == 1) { enqueue_uniform<LV>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE, TRACE ? j + 1 : 0u); continue; }
         {   // A list that holds a large share of the proof asks for more than the quarter of the pool the rule above keeps
             // free: if the two pushes of this clause could not both grow their lists (list_push_uniform's policy), lay the
             // lists out densely first - every list then has two free slots at least, and the dense layout always fits
@@ -3050,11 +3265,14 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
                 if (w.status != MS_ST_RUNNING) break;
             }
         }
-        if (add_learnt<LV>(w, sh, L, cnt, 1u | MS_LBD_NOLOG) < 0) break;
+        const int cref = add_learnt<LV>(w, sh, L, cnt, 1u | MS_LBD_NOLOG);
+        if (cref < 0) break;
+        if (TRACE && w.lane == 0) WKA(uint32_t, remap)[(uint32_t)cref - sh.n_orig] = j;
     }
     if (w.status == MS_ST_RUNNING && j >= b) w.status = MS_ST_SAT;
     wave_fence();
     if (w.lane == 0) {
+        if (TRACE) ((Gp<uint32_t>)tr.used)[wid] = log_used;
         cur[0] = (int32_t)j;
         Gp<u64> cnt64 = (Gp<u64>)(cur + 4);
         cnt64[0] += n_checked;

@@ -130,7 +130,7 @@ struct MsLayout {
     uint64_t learnt_buf;  // int32  [n_vars+1]   clause under construction
     uint64_t toclear;     // int32  [n_vars+1]   vars touched by analysis
     uint64_t lvl_stamp;   // uint32 [n_vars+2]   LBD computation
-    uint64_t remap;       // uint32 [learnt_cap] reduceDB old->new
+    uint64_t remap;       // uint32 [learnt_cap] reduceDB old->new; in a traced proof check (no reduction): the lemma a learnt slot holds
     uint64_t overflow;    // int32  [3*MS_OVERFLOW_CAP]  (list, cref, blocker)
     uint64_t assumps;     // int32  [assump_cap]
     uint64_t script;      // int32  [script_cap]  decisions for propagate_batch
@@ -185,6 +185,27 @@ struct MsState {
     // because the learnt store had no room for them even after a reduction
     uint64_t n_pressure_reduces, n_pool_rebuilds, n_imports_dropped_full;
 };
+
+// Dependency log of a traced proof check (ms_rup_kernel<LV, true>, mi355sat_trim_proof).  A buffer of its own, one region of
+// `words` words per worker, written by that worker alone; used[w] = words of region w in use, read when a launch begins and
+// written when it ends (the host drains every region after every launch and zeroes the cursors).  Per traced item one
+// header and then its records, MS_TR_REC words each (one 16-byte store):
+//   header  { item | MS_TR_REFUTED, records, 0, 0 }   MS_TR_REFUTED: not the check of lemma `item` but the conflict of
+//                                                     the database itself, found when the worker stood in front of `item`
+//   record  { tag << 28 | pos, a, b, c }   pos: trail position of the literal the clause implied - the conflicting (or
+//                                          satisfying) clause itself has the highest of its item
+//     MS_TR_LONG        a = index of the original long clause                          c = implied literal, -1: the conflict
+//     MS_TR_BIN         a, b = the binary clause's literals (a the implied one)
+//     MS_TR_TERN        a, b, c = the ternary clause's literals (a the implied one)
+//     MS_TR_LEMMA       a = lemma index (an attached lemma of two and more free literals) c = implied literal, -1: the conflict
+//     MS_TR_UNIT        a = the literal of a unit clause of the caller
+//     MS_TR_UNIT_LEMMA  a = index of the lemma that was unit when it was attached         c = implied literal
+// Literals are device literals.  One item has at most n_vars + 2 records.
+struct MsTrace { uint32_t* log; uint32_t* used; uint32_t words, pad; };
+#define MS_TR_REC 4
+#define MS_TR_REFUTED 0x80000000u
+enum { MS_TR_LONG = 1, MS_TR_BIN = 2, MS_TR_TERN = 3, MS_TR_LEMMA = 4, MS_TR_UNIT = 5, MS_TR_UNIT_LEMMA = 6 };
+#define MS_TR_ITEM_WORDS(n_vars) (MS_TR_REC * ((uint64_t)(n_vars) + 3))     // the most one item takes: header + n_vars + 2 records
 
 // Launch parameters of one slice.
 struct MsParams {

@@ -14,11 +14,13 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <map>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <queue>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/mi355sat.h"
@@ -411,6 +413,19 @@ struct mi355sat {
     uint64_t sat_clauses = UINT64_MAX;         // stats.n_clauses when a solve / batch last answered SAT
     uint32_t core_min_round = 0;
     uint32_t proof_chunk = 0;                  // test hook (mi355sat_debug_proof_check_chunk): lemmas per worker and launch of a proof check
+    uint32_t trim_log_words = 0;               // test hook (mi355sat_debug_trim_log): words per worker of a traced check's dependency log
+    // What the last mi355sat_trim_proof found a valid proof to rest on; dropped by the next trim_proof / check_proof, a clause
+    // added, a sweep begun.  Indices: caller clauses 0-based in the order they were added, lemmas 0-based, both ascending.
+    struct Trim {
+        bool valid = false, hints = false;
+        bool no_lines = false;                 // a tautological target: nothing to derive
+        uint64_t n_clauses = 0, n_lemmas = 0;
+        std::vector<uint64_t> core, lemmas;
+        std::vector<int32_t> lits;             // DIMACS literals of the needed lemmas in order, then the target's
+        std::vector<uint64_t> offs{0};
+        std::vector<std::vector<uint64_t>> hint;   // (hints) per needed lemma, then the target: LRAT ids in the order a checker propagates them
+        void drop() { *this = Trim(); }
+    } trim;
     // warm incremental solve (mi355sat_set_incremental): what the last mi355sat_solve() left on the device, and what was
     // attached to it since
     struct Incremental {
@@ -2797,7 +2812,7 @@ int read_proof_file(mi355sat& s, const char* path, std::vector<int32_t>& words) 
 }
 
 SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32_t* lits, const uint32_t* offs, const uint8_t* skip,
-                       uint32_t n_items, unsigned long long* mins) {
+                       uint32_t n_items, unsigned long long* mins, const MsTrace* trace = nullptr) {
     MsParams prm{};
     prm.n_workers = active;
     prm.max_groups = s.opts.max_groups > 0 ? s.opts.max_groups : MS_MAX_GROUPS;
@@ -2806,8 +2821,12 @@ SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32
     prm.stop_flag = s.stop_flag;
     const mi355sat_search_build build = choose_build(active, s.lds_val_bytes, s.lds_val, s.opts.lds_val, s.opts.one_per_simd, 1);
     HIPCHK(hipEventRecord(s.ev0, s.stream));
-    if (build.lds) hipLaunchKernelGGL(ms_rup_kernel<true>, dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins);
-    else hipLaunchKernelGGL(ms_rup_kernel<false>, dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins);
+    const MsTrace none{};
+    if (trace) {
+        if (build.lds) hipLaunchKernelGGL((ms_rup_kernel<true, true>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, *trace);
+        else hipLaunchKernelGGL((ms_rup_kernel<false, true>), dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, *trace);
+    } else if (build.lds) hipLaunchKernelGGL((ms_rup_kernel<true, false>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, none);
+    else hipLaunchKernelGGL((ms_rup_kernel<false, false>), dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, none);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev1, s.stream));
     HIPCHK(hipEventSynchronize(s.ev1));
@@ -2818,7 +2837,189 @@ SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32
     return SliceResult{ms};
 }
 
-int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info) {
+// ---- trimming a checked proof (mi355sat_trim_proof) -----------------------------------------------------------------------
+// The traced check's host side: the device names what a check rested on by what the worker holds - a long clause's index,
+// the literals of a binary or ternary clause, a unit's literal, a lemma's index; here those become the caller's clause
+// indices and lemma indices, one list per checked item in the order a checker has to propagate them (the trail positions).
+// normalise / build_csr drop tautologies and duplicates: a clause that occurs twice is named by its lowest index.
+struct TrimRun {
+    uint32_t flags = 0;
+    mi355sat_trim_info* out = nullptr;
+    uint64_t n_clauses = 0;
+    // device identity -> caller clause index (identity_order: a device literal is the caller's, 2 * (var - 1) + neg)
+    std::vector<uint64_t> long_idx;
+    std::map<std::array<int32_t, 3>, uint64_t> short_idx;       // sorted literals; a binary clause's third is INT32_MAX
+    std::unordered_map<int32_t, uint64_t> unit_idx;
+    // what the device reported: ids (caller clause i: i; lemma j: n_clauses + j) in hint order
+    std::vector<std::vector<uint64_t>> deps;
+    std::vector<uint8_t> have;
+    struct Refutation { std::vector<uint64_t> ids; std::vector<int32_t> implied; };   // implied: the literal each clause gave, -1: the conflict
+    std::map<uint64_t, Refutation> refuted;                       // by the item the worker stood in front of
+    DevBuf<uint32_t> d_log, d_used;
+    uint32_t words = 0;
+};
+
+static std::array<int32_t, 3> short_key(int32_t a, int32_t b, int32_t c) {
+    std::array<int32_t, 3> k{a, b, c};
+    std::sort(k.begin(), k.end());
+    return k;
+}
+
+// The reverse maps, clause by clause as normalise sees them.  unsat_core: where normalise stops (an empty clause, or a
+// unit against an earlier unit), the clause or the pair that is - the whole core when the formula falls before any launch.
+void trim_maps(const mi355sat& s, TrimRun& T, std::vector<uint64_t>& unsat_core) {
+    std::vector<int32_t> tmp;
+    T.n_clauses = s.offs.size() - 1;
+    for (uint64_t c = 0; c < T.n_clauses; c++) {
+        tmp.clear();
+        for (uint64_t k = s.offs[c]; k < s.offs[c + 1]; k++) tmp.push_back(to_internal(s.lits[k]));
+        std::sort(tmp.begin(), tmp.end());
+        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+        bool taut = false;
+        for (size_t i = 0; i + 1 < tmp.size(); i++) taut = taut || (tmp[i] ^ 1) == tmp[i + 1];
+        if (taut) continue;
+        if (tmp.empty()) { if (unsat_core.empty()) unsat_core = {c}; }
+        else if (tmp.size() == 1) {
+            auto other = T.unit_idx.find(tmp[0] ^ 1);
+            if (other != T.unit_idx.end() && unsat_core.empty()) unsat_core = {other->second, c};
+            T.unit_idx.emplace(tmp[0], c);
+        } else if (tmp.size() == 2) T.short_idx.emplace(short_key(tmp[0], tmp[1], INT32_MAX), c);
+        else if (tmp.size() == 3) T.short_idx.emplace(short_key(tmp[0], tmp[1], tmp[2]), c);
+        else T.long_idx.push_back(c);
+    }
+}
+
+// Every worker's region of the dependency log after a launch: parsed, mapped, the cursors reset.
+int trim_drain(mi355sat& s, TrimRun& T, uint32_t S, uint32_t n_items) {
+    std::vector<uint32_t> used(S), buf;
+    HIPCHK(hipMemcpy(used.data(), T.d_used.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    bool any = false;
+    std::vector<std::array<int64_t, 3>> recs;        // pos, id, implied
+    auto fail = [&](const char* what) { s.err = std::string("proof trim: ") + what; return MI355SAT_ERR_HIP; };
+    for (uint32_t w = 0; w < S; w++) {
+        if (!used[w]) continue;
+        any = true;
+        if (used[w] > T.words || used[w] % MS_TR_REC) return fail("a log cursor out of range");
+        buf.resize(used[w]);
+        HIPCHK(hipMemcpy(buf.data(), T.d_log.p + (size_t)w * T.words, (size_t)used[w] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < buf.size();) {
+            const uint32_t item = buf[i] & ~MS_TR_REFUTED, n = buf[i + 1];
+            const bool refuted = (buf[i] & MS_TR_REFUTED) != 0;
+            if (item >= n_items + (refuted ? 1u : 0u) || (uint64_t)n > (uint64_t)s.L.n_vars + 2 || i + MS_TR_REC * ((size_t)n + 1) > buf.size())
+                return fail("a malformed log item");
+            recs.clear();
+            for (uint32_t r = 0; r < n; r++) {
+                const int32_t* x = (const int32_t*)&buf[i + MS_TR_REC * ((size_t)r + 1)];
+                const uint32_t tag = (uint32_t)x[0] >> 28;
+                const int64_t pos = x[0] & 0x0fffffff;
+                int64_t id = -1, implied = -1;
+                if (tag == MS_TR_LONG) { if ((uint32_t)x[1] < T.long_idx.size()) id = (int64_t)T.long_idx[x[1]]; implied = x[3]; }
+                else if (tag == MS_TR_BIN || tag == MS_TR_TERN) {
+                    auto it = T.short_idx.find(short_key(x[1], x[2], tag == MS_TR_BIN ? INT32_MAX : x[3]));
+                    if (it != T.short_idx.end()) id = (int64_t)it->second;
+                    implied = x[1];
+                } else if (tag == MS_TR_UNIT) {
+                    auto it = T.unit_idx.find(x[1]);
+                    if (it != T.unit_idx.end()) id = (int64_t)it->second;
+                    implied = x[1];
+                } else if (tag == MS_TR_LEMMA || tag == MS_TR_UNIT_LEMMA) {
+                    if ((uint32_t)x[1] < item) id = (int64_t)(T.n_clauses + (uint32_t)x[1]);
+                    implied = x[3];
+                }
+                if (id < 0) return fail("a record names no clause of the caller and no earlier lemma");
+                recs.push_back({pos, id, implied});
+            }
+            std::sort(recs.begin(), recs.end());
+            std::vector<uint64_t> ids;
+            for (auto& r : recs) ids.push_back((uint64_t)r[1]);
+            if (refuted) {
+                TrimRun::Refutation& R = T.refuted[item];
+                R.ids.swap(ids);
+                R.implied.clear();
+                for (size_t k = 0; k < recs.size(); k++) R.implied.push_back(k + 1 == recs.size() ? -1 : (int32_t)recs[k][2]);
+            } else {
+                T.deps[item].swap(ids);
+                T.have[item] = 1;
+            }
+            T.out->dep_records += n;
+            i += MS_TR_REC * ((size_t)n + 1);
+        }
+    }
+    if (any) {
+        T.out->log_drains++;
+        HIPCHK(hipMemsetAsync(T.d_used.p, 0, S * sizeof(uint32_t), s.stream));
+        HIPCHK(hipStreamSynchronize(s.stream));
+    }
+    return 0;
+}
+
+// From the target backwards: a needed item's clauses enter the core, its lemmas become needed.  dl / doff / skip: the proof as
+// the device read it (the target's device literals decide which hints of a level-0 refutation a non-empty target keeps).
+int trim_reach(mi355sat& s, TrimRun& T, const ProofLemmas& pf, const std::vector<uint8_t>& skip, const std::vector<int32_t>& dl,
+               const std::vector<uint32_t>& doff, const mi355sat_proof_info& info) {
+    auto fail = [&](const char* what) { s.err = std::string("proof trim: ") + what; return MI355SAT_ERR_HIP; };
+    const uint64_t nl = pf.n_lemmas, nc = T.n_clauses;
+    std::vector<uint8_t> needed(nl, 0), core(nc, 0);
+    std::vector<uint64_t> target_ids;
+    mi355sat::Trim& R = s.trim;
+    R.drop();
+    if (skip[nl]) R.no_lines = true;
+    else if (info.refuted_at != UINT64_MAX) {
+        auto it = T.refuted.find(info.refuted_at);
+        if (it == T.refuted.end()) return fail("no worker traced the refutation");
+        // under the negated target a clause whose literal the target assumes is satisfied, and one that gives a literal of
+        // the target ends the derivation
+        std::unordered_map<int32_t, int> tl;
+        for (uint32_t k = doff[nl]; k < doff[nl + 1]; k++) tl[dl[k]] = 1;
+        for (size_t k = 0; k < it->second.ids.size(); k++) {
+            const int32_t x = it->second.implied[k];
+            if (x >= 0 && tl.count(x ^ 1)) continue;
+            target_ids.push_back(it->second.ids[k]);
+            if (x >= 0 && tl.count(x)) break;
+        }
+    } else {
+        if (!T.have[nl]) return fail("the target's check was not traced");
+        target_ids = T.deps[nl];
+    }
+    const uint64_t upper = std::min<uint64_t>(nl, info.refuted_at);
+    auto use = [&](const std::vector<uint64_t>& ids, uint64_t below) {
+        for (uint64_t id : ids) {
+            if (id < nc) core[id] = 1;
+            else if (id - nc < below) needed[id - nc] = 1;
+            else return false;
+        }
+        return true;
+    };
+    if (!use(target_ids, upper)) return fail("the target rests on a lemma behind the refutation");
+    for (uint64_t j = upper; j-- > 0;) {
+        if (!needed[j]) continue;
+        if (!T.have[j]) return fail("a needed lemma's check was not traced");
+        if (!use(T.deps[j], j)) return fail("a lemma rests on a later one");
+    }
+    R.n_clauses = nc;
+    R.n_lemmas = nl;
+    R.hints = (T.flags & MI355SAT_TRIM_HINTS) != 0;
+    for (uint64_t c = 0; c < nc; c++) if (core[c]) R.core.push_back(c);
+    auto lrat = [&](const std::vector<uint64_t>& ids) {
+        std::vector<uint64_t> h;
+        for (uint64_t id : ids) h.push_back(id + 1);
+        return h;
+    };
+    for (uint64_t j = 0; j <= nl; j++) {
+        if (j < nl && !needed[j]) continue;
+        if (j < nl) R.lemmas.push_back(j);
+        R.lits.insert(R.lits.end(), pf.lits.begin() + pf.offs[j], pf.lits.begin() + pf.offs[j + 1]);
+        R.offs.push_back(R.lits.size());
+        if (R.hints) R.hint.push_back(lrat(j < nl ? T.deps[j] : target_ids));
+    }
+    R.valid = true;
+    T.out->core_clauses = R.core.size();
+    T.out->lemmas_needed = R.lemmas.size();
+    return 0;
+}
+
+int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info,
+                     TrimRun* T = nullptr) {
     for (uint64_t i = 0; i < n_target; i++) {
         if (target[i] == 0 || target[i] == INT32_MIN) { s.err = "proof target: literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
         if (var_of(target[i]) > s.max_var) { s.err = "proof target: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
@@ -2842,9 +3043,28 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
     s.ph.on_device = false;
     Prepared P;
     prepare(s, /*simplify=*/false, P, /*identity_order=*/true);
+    std::vector<uint64_t> unsat_core;
+    if (T) trim_maps(s, *T, unsat_core);
     if (P.unsat) {               // an empty clause or contradictory units among the caller's clauses
         info.refuted_at = 0;
         info.valid = 1;
+        if (T) {                 // the core is that clause or that pair: one LRAT line, the target's
+            if (unsat_core.empty()) { s.err = "proof trim: the refuting clauses were not found"; return MI355SAT_ERR_HIP; }
+            mi355sat::Trim& R = s.trim;
+            R.n_clauses = T->n_clauses;
+            R.n_lemmas = pf.n_lemmas;
+            R.hints = (T->flags & MI355SAT_TRIM_HINTS) != 0;
+            R.core = unsat_core;
+            std::sort(R.core.begin(), R.core.end());
+            R.lits.assign(target, target + n_target);
+            R.offs.push_back(R.lits.size());
+            if (R.hints) {
+                R.hint.emplace_back();
+                for (uint64_t c : unsat_core) R.hint.back().push_back(c + 1);
+            }
+            R.valid = true;
+            T->out->core_clauses = R.core.size();
+        }
         return 0;
     }
     if (P.n_vars == 0) {         // no variable, no clause: only empty lemmas are possible, and none is RUP
@@ -2902,6 +3122,19 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
     d_offs.upload(doff, s.stream);
     d_skip.upload(skip, s.stream);
     d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
+    MsTrace mt{};
+    if (T) {
+        // a worker ends its launch when its region has less room than two items of the largest size: never size one below that
+        const uint64_t floor_words = 2 * MS_TR_ITEM_WORDS(P.n_vars);
+        const uint64_t rule = std::min<uint64_t>(1u << 18, (1u << 26) / S);
+        T->words = (uint32_t)std::max<uint64_t>(floor_words, s.trim_log_words ? s.trim_log_words : rule);
+        T->out->log_words_per_worker = T->words;
+        T->d_log.alloc((size_t)S * T->words);
+        T->d_used.upload(std::vector<uint32_t>(S, 0u), s.stream);
+        T->deps.assign(n_items, {});
+        T->have.assign(n_items, 0);
+        mt = MsTrace{T->d_log.p, T->d_used.p, T->words, 0};
+    }
     HIPCHK(hipStreamSynchronize(s.stream));
     const uint32_t chunk = s.proof_chunk;
     const double k0 = s.stats.kernel_seconds;
@@ -2909,9 +3142,10 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
     bool interrupted = false;
     for (;;) {
         if (s.interrupted.load()) { interrupted = true; break; }
-        launch_rup(s, S, chunk, d_lits.p, d_offs.p, d_skip.p, n_items, d_mins.p);
+        launch_rup(s, S, chunk, d_lits.p, d_offs.p, d_skip.p, n_items, d_mins.p, T ? &mt : nullptr);
         info.launches++;
         gather_states(s, sts);
+        if (T) if (int rc = trim_drain(s, *T, S, n_items)) return rc;
         bool running = false;
         for (uint32_t w = 0; w < S; w++) {
             if (sts[w].status < 0) {
@@ -2950,16 +3184,29 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
         return MI355SAT_ERR_HIP;
     }
     info.valid = info.first_failed == UINT64_MAX ? 1 : 0;
+    if (T && info.valid == 1) return trim_reach(s, *T, pf, skip, dl, doff, info);
     return 0;
 }
 
-int check_proof_entry(mi355sat* s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info* out) {
+// trim (may be null): the traced check of mi355sat_trim_proof, whose result stays on the handle.
+int check_proof_entry(mi355sat* s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info* out,
+                      mi355sat_trim_info* trim = nullptr, uint32_t flags = 0) {
     mi355sat_proof_info info{};
     const double t0 = now_s();
-    const int rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info); });
+    s->trim.drop();
+    int rc;
+    if (trim) {
+        TrimRun T;
+        *trim = mi355sat_trim_info{};
+        T.flags = flags;
+        T.out = trim;
+        rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info, &T); });
+        if (rc < 0 || info.valid != 1) s->trim.drop();
+    } else rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info); });
     info.seconds = now_s() - t0;
     if (rc < 0) go_cold(*s, MI355SAT_COLD_FIRST);
-    *out = info;
+    if (trim) trim->check = info;
+    else *out = info;
     return rc;
 }
 
@@ -3064,6 +3311,7 @@ static int add_clause_impl(mi355sat* s, const int32_t* l, uint64_t n) {
     s->lits.insert(s->lits.end(), l, l + n);
     s->offs.push_back(s->lits.size());
     s->core.valid = false;     // IPASIR: adding leaves the UNSAT state
+    s->trim.drop();            // (clause indices mean something else now)
     s->stats.n_clauses++;
     s->stats.max_var = s->max_var;
     s->stats.avg_clause_len = (double)s->lits.size() / (double)s->stats.n_clauses;
@@ -3250,6 +3498,92 @@ int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch
     return 0;
 }
 
+int mi355sat_trim_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
+                        uint32_t segments, uint32_t flags, mi355sat_trim_info* out) {
+    if (!s || !out || (n_words && !proof) || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
+    if (s->sweep) { s->err = "trim_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = "trim_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    ProofLemmas pf;
+    if (int rc = guarded(s, GUARD_HOST, [&] { return parse_proof_words(*s, proof, n_words, pf); })) return rc;
+    return check_proof_entry(s, pf, target, n_target, segments, nullptr, out, flags);
+}
+
+int mi355sat_trim_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
+                             uint32_t flags, mi355sat_trim_info* out) {
+    if (!s || !out || !path || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
+    if (s->sweep) { s->err = "trim_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = "trim_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    ProofLemmas pf;
+    if (int rc = guarded(s, GUARD_HOST, [&] {
+            std::vector<int32_t> words;
+            if (int e = read_proof_file(*s, path, words)) return e;
+            return parse_proof_words(*s, words.data(), words.size(), pf);
+        })) return rc;
+    return check_proof_entry(s, pf, target, n_target, segments, nullptr, out, flags);
+}
+
+static int trim_result(mi355sat* s) {
+    if (s->trim.valid) return 0;
+    s->err = "no trimmed proof: the last call was not a mi355sat_trim_proof() that found the proof valid";
+    return MI355SAT_ERR_STATE;
+}
+
+static int copy_indices(mi355sat* s, const std::vector<uint64_t>& v, uint64_t* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = v.size();
+    if (!out) return 0;
+    if (cap < v.size()) { s->err = "index buffer too small"; return MI355SAT_ERR_ARG; }
+    std::copy(v.begin(), v.end(), out);
+    return 0;
+}
+
+int mi355sat_trim_core(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (int rc = trim_result(s)) return rc;
+    return copy_indices(s, s->trim.core, out, cap, n);
+}
+
+int mi355sat_trim_lemmas(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (int rc = trim_result(s)) return rc;
+    return copy_indices(s, s->trim.lemmas, out, cap, n);
+}
+
+// One clause per line: (LRAT) its id first, the literals, 0, (LRAT) the hints and another 0.
+static int write_trimmed(mi355sat* s, const char* path, bool lrat) {
+    if (!s || !path) return MI355SAT_ERR_ARG;
+    if (int rc = trim_result(s)) return rc;
+    const mi355sat::Trim& R = s->trim;
+    if (lrat && !R.hints) { s->err = "trim_write_lrat(): the proof was trimmed without MI355SAT_TRIM_HINTS"; return MI355SAT_ERR_STATE; }
+    return guarded(s, GUARD_HOST, [&] {
+        FILE* f = fopen(path, "w");
+        if (!f) { s->err = std::string("cannot open ") + path; return MI355SAT_ERR_ARG; }
+        const size_t n_lines = R.no_lines && lrat ? 0 : R.offs.size() - 1;
+        for (size_t i = 0; i < n_lines; i++) {
+            const bool is_target = i + 1 == R.offs.size() - 1;
+            if (lrat) fprintf(f, "%llu ", (unsigned long long)(R.n_clauses + 1 + (is_target ? R.n_lemmas : R.lemmas[i])));
+            for (uint64_t k = R.offs[i]; k < R.offs[i + 1]; k++) fprintf(f, "%d ", R.lits[k]);
+            fputs("0", f);
+            if (lrat) {
+                for (uint64_t h : R.hint[i]) fprintf(f, " %llu", (unsigned long long)h);
+                fputs(" 0", f);
+            }
+            fputs("\n", f);
+        }
+        const bool bad = ferror(f) != 0;
+        if (fclose(f) != 0 || bad) { s->err = std::string("cannot write ") + path; return MI355SAT_ERR_ARG; }
+        return 0;
+    });
+}
+
+int mi355sat_trim_write_drup(mi355sat* s, const char* path) { return write_trimmed(s, path, false); }
+int mi355sat_trim_write_lrat(mi355sat* s, const char* path) { return write_trimmed(s, path, true); }
+
+int mi355sat_debug_trim_log(mi355sat* s, uint32_t words_per_worker) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->trim_log_words = words_per_worker;
+    return 0;
+}
+
 int mi355sat_set_incremental(mi355sat* s, int on) {
     if (!s) return MI355SAT_ERR_ARG;
     s->inc.on = on != 0;
@@ -3414,6 +3748,7 @@ int mi355sat_sweep_begin(mi355sat* s, const int32_t* assumps, const uint64_t* as
         delete s->sweep;
         s->sweep = new SweepHolder;
         s->sweep->base = s->stats;
+        s->trim.drop();
         go_cold(*s, MI355SAT_COLD_OTHER_SEARCH);
         return sweep_begin(*s, s->sweep->sw, assump, aoff, (uint32_t)n_instances, false);
     });

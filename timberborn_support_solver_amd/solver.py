@@ -130,6 +130,19 @@ class Mi355SatProofInfo(ctypes.Structure):   # mi355sat_proof_info
         return d
 
 
+class Mi355SatTrimInfo(ctypes.Structure):   # mi355sat_trim_info
+    _fields_ = [("check", Mi355SatProofInfo)] + \
+               [(n, ctypes.c_uint64) for n in ("core_clauses", "lemmas_needed", "dep_records", "log_drains", "log_words_per_worker")]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "check"}
+        d["check"] = self.check.as_dict()
+        return d
+
+
+TRIM_HINTS = 1   # MI355SAT_TRIM_HINTS
+
+
 class ColdReason(enum.IntEnum):  # MI355SAT_COLD_*: why a solve() with the incremental mode on started cold
     NONE = 0
     FIRST = 1
@@ -199,6 +212,15 @@ def _bind(L):
     L.mi355sat_check_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
     L.mi355sat_check_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
     L.mi355sat_debug_proof_check_chunk.argtypes = [vp, ctypes.c_uint32]
+    L.mi355sat_trim_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.POINTER(Mi355SatTrimInfo)]
+    L.mi355sat_trim_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                           ctypes.POINTER(Mi355SatTrimInfo)]
+    L.mi355sat_trim_core.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_trim_lemmas.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_trim_write_drup.argtypes = [vp, ctypes.c_char_p]
+    L.mi355sat_trim_write_lrat.argtypes = [vp, ctypes.c_char_p]
+    L.mi355sat_debug_trim_log.argtypes = [vp, ctypes.c_uint32]
     L.mi355sat_set_incremental.argtypes = [vp, ctypes.c_int]
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
@@ -372,6 +394,62 @@ class Mi355Sat:
     def debug_proof_check_chunk(self, max_lemmas_per_launch=0):
         """Test hook: at most this many lemmas per worker and launch of check_proof (0 = the default, time-bounded)."""
         self._check(self._L.mi355sat_debug_proof_check_chunk(self._h, int(max_lemmas_per_launch)), "debug_proof_check_chunk")
+
+    # ---- trimmed proofs: the clause core, the needed lemmas, LRAT (include/mi355sat.h)
+    def _indices(self, fn, what):
+        n = ctypes.c_uint64(0)
+        self._check(fn(self._h, None, 0, ctypes.byref(n)), what)
+        out = np.zeros(n.value, dtype=np.uint64)
+        self._check(fn(self._h, _p(out), n.value, ctypes.byref(n)), what)
+        return [int(i) for i in out[:n.value]]
+
+    def trim_core(self):
+        """After a trim_proof() that found the proof valid: the 0-based indices of this handle's clauses the derivation of
+        the target rests on, ascending.  Raises SolverError (ERR_STATE) in any other state."""
+        return self._indices(self._L.mi355sat_trim_core, "trim_core")
+
+    def trim_lemmas(self):
+        """... and the 0-based indices of the lemmas it needs, ascending."""
+        return self._indices(self._L.mi355sat_trim_lemmas, "trim_lemmas")
+
+    def _trimmed(self, info):
+        d = info.as_dict()
+        valid = d["check"]["valid"] == 1
+        d["core"] = self.trim_core() if valid else None
+        d["lemmas"] = self.trim_lemmas() if valid else None
+        return d
+
+    def trim_proof(self, proof, target=(), segments=0, hints=False):
+        """check_proof() in the tracing build of the checker: "check" is check_proof's dict for the same inputs; where it
+        says valid, "core" and "lemmas" are the clauses of this handle and the lemmas of the proof that the derivation of
+        `target` rests on (None otherwise).  hints = True keeps what trim_write_lrat() needs.  Which clauses make the core
+        may differ with `segments` and from run to run; the verdict does not."""
+        pr = np.ascontiguousarray(proof, dtype=np.int32)
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatTrimInfo()
+        self._check(self._L.mi355sat_trim_proof(self._h, _p(pr), pr.size, _p(tg), tg.size, int(segments),
+                                                TRIM_HINTS if hints else 0, ctypes.byref(info)), "trim_proof")
+        return self._trimmed(info)
+
+    def trim_proof_file(self, path, target=(), segments=0, hints=False):
+        """The same for a DRUP text file as set_proof_path() writes it."""
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatTrimInfo()
+        self._check(self._L.mi355sat_trim_proof_file(self._h, str(path).encode(), _p(tg), tg.size, int(segments),
+                                                     TRIM_HINTS if hints else 0, ctypes.byref(info)), "trim_proof_file")
+        return self._trimmed(info)
+
+    def trim_write_drup(self, path):
+        """The needed lemmas in order, then the target, as DRUP text."""
+        self._check(self._L.mi355sat_trim_write_drup(self._h, str(path).encode()), "trim_write_drup")
+
+    def trim_write_lrat(self, path):
+        """The same lines as LRAT: clause i of this handle has id i + 1, lemma j has n_clauses + 1 + j.  Needs hints = True."""
+        self._check(self._L.mi355sat_trim_write_lrat(self._h, str(path).encode()), "trim_write_lrat")
+
+    def debug_trim_log(self, words=0):
+        """Test hook: words per worker of trim_proof's dependency log (0 = the rule; never below two items of the largest size)."""
+        self._check(self._L.mi355sat_debug_trim_log(self._h, int(words)), "debug_trim_log")
 
     # ---- phase hints (rustsat PhaseLit's place; seeded, not forced: include/mi355sat.h)
     def phase(self, lit):
