@@ -437,7 +437,12 @@ int mi355sat_debug_search_build_rule(uint32_t active, uint32_t lds_val_bytes, in
  *   - the clauses attached warm since the last cold start would take more than a quarter of a worker's learnt-clause
  *     slots or literal store (they are kept there for ever), or a worker's store or watch pool ran full attaching them;
  *   - mi355sat_solve_batch(), mi355sat_sweep_begin() or mi355sat_propagate_batch() ran on the handle in between (they
- *     stay cold and take the device state over).
+ *     stay cold and take the device state over), or mi355sat_check_proof() / _trim_proof(), or a
+ *     mi355sat_minimize_core() that posed candidates: MI355SAT_COLD_OTHER_SEARCH;
+ *   - the mode was switched off in between (that drops what is resident, also when it is switched on again at once), or
+ *     mi355sat_debug_set_schedule() changed what a worker's state depends on, or the solve before logged a proof (it
+ *     leaves nothing resident): MI355SAT_COLD_FIRST.
+ * mi355sat_phase() / _set_phases() and an interrupt never make a solve start cold.
  * A handle whose formula was refuted without assumptions answers every later solve UNSAT with the empty core at once.
  * The IPASIR state rules do not change: assumptions are consumed, failed / core are valid straight after UNSAT only,
  * an interrupt is not lost; an interrupted or budget-exhausted solve leaves the handle warm.  Returns 0. */
@@ -450,7 +455,7 @@ int mi355sat_set_incremental(mi355sat* s, int on);
 #define MI355SAT_COLD_PROOF 4
 #define MI355SAT_COLD_CUBE_SPLIT 5
 #define MI355SAT_COLD_PINNED_SHARE 6
-#define MI355SAT_COLD_OTHER_SEARCH 7    /* solve_batch / sweep_* / propagate_batch in between */
+#define MI355SAT_COLD_OTHER_SEARCH 7    /* solve_batch / sweep_* / propagate_batch / check_proof / trim_proof / minimize_core in between */
 #define MI355SAT_COLD_ASSUMP_CAP 8
 #define MI355SAT_COLD_DEVICE_FULL 9     /* a worker's learnt store or watch pool ran full during the attach */
 /* Test hook: what the incremental mode did on this handle so far. */
@@ -529,7 +534,10 @@ int mi355sat_debug_capacities(const mi355sat* s, mi355sat_capacity_info* out);
  * caller's formula alone (the tests prove it with the oracle), so it may be attached under any assumptions.  Both
  * calls are made between two mi355sat_sweep_step() of a running sweep; without one (or with the exchange off) they
  * do nothing.  export: out may be NULL to size the buffer (nothing is consumed); records that do not fit cap_words
- * wait for the next call. */
+ * wait for the next call.  import: *n_records counts the records taken; a record is passed over when it is longer than
+ * the ring's 31 literals, names a variable this handle does not know or has eliminated (opts.simp = 2), or holds a
+ * literal and its negation once it is written in this handle's variables (its own equivalent-literal substitution may
+ * join what the exporter kept apart); a literal that the substitution makes appear twice is kept once. */
 int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_t* n_words, uint64_t* n_records);
 int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words, uint64_t* n_records /* may be NULL */);
 

@@ -41,12 +41,13 @@ def sweep_cnf(terrain, pset, k_max=8):
 class Checked:
     """A solver handle plus everything added to it so far; solve() checks the answer against the oracle."""
 
-    def __init__(self, cnf, solver, incremental=True, n_vars=None):
+    def __init__(self, cnf, solver, incremental=True, n_vars=None, run=None):
         self.s = solver
         self.n_vars = (cnf.n_vars + N_FRESH) if n_vars is None else n_vars
         self.clauses = []
         self.base = cnf
         self.log = []
+        self.run = run or (lambda fn: fn())        # e.g. every solve under a deadline (tests/incremental_cases.py)
         if incremental:
             self.s.set_incremental(True)
         self.s.add_cnf(cnf.lits, cnf.offsets)
@@ -70,10 +71,14 @@ class Checked:
         o.reserve(self.n_vars)
         return o
 
-    def solve(self, assumptions=(), expect=None):
+    def solve(self, assumptions=(), expect=None, may_stop=False):
+        """may_stop: the solve may also end undecided (an interrupt the caller sent, a conflict budget): logged, not judged."""
         assumptions = [int(l) for l in assumptions]
         self.n_vars = max([self.n_vars] + [abs(l) for l in assumptions])
-        r = self.s.solve(assumptions)
+        r = self.run(lambda: self.s.solve(assumptions))
+        if may_stop and r == SolverResult.Interrupted:
+            self.log.append((r, None))
+            return r
         want = self.oracle().solve(assumptions)
         assert r.value == want, (r, want, assumptions, self.s.debug_incremental())
         if expect is not None:

@@ -3953,7 +3953,13 @@ int mi355sat_debug_search_build_rule(uint32_t active, uint32_t lds_val_bytes, in
 // Records travel as [lbd, DIMACS literals ..., 0] in the CALLER's variables: a ring record is a consequence of the
 // simplified formula this handle searches, hence of the caller's formula (simplification only derives consequences,
 // substituted variables are written as their representatives), so another handle - whose own simplification may have
-// come out differently - can map it into its own variables and attach it.
+// come out differently - can map it into its own variables and attach it.  The import normalises what the mapping leaves:
+// a record that names both members of an equivalence class of THIS handle arrives as one device literal twice, or as a
+// literal and its negation - and a clause in a worker's store holds every variable at most once (conflict analysis marks
+// and counts the variables of a reason one lane each: a variable presented by two lanes is counted twice, the walk runs
+// off the trail, MS_ST_ERR_INTERNAL).  So the mapped record is sorted, a repeated literal kept once, and a record with a
+// literal and its negation (true whatever the assignment) dropped and not counted, exactly as warm_begin treats a clause
+// the caller adds.
 #define MS_FOREIGN_PRODUCER 0x3ffffu    // producer id of records that came from another handle: never handed out again
 int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_t* n_words, uint64_t* n_records) {
     if (!s || !n_words || !n_records) return MI355SAT_ERR_ARG;
@@ -4024,6 +4030,12 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
             if (i >= n_words) { s->err = "share_import: clause without terminator"; return MI355SAT_ERR_ARG; }
             i++;   // the terminator
             if (!ok || sz < 1) continue;
+            // as warm_begin does for an added clause: sorted, a repeated device literal once, a tautology not at all
+            std::sort(rec + 1, rec + 1 + sz);
+            sz = (int)(std::unique(rec + 1, rec + 1 + sz) - (rec + 1));
+            bool taut = false;
+            for (int j = 1; j < sz; j++) taut = taut || (rec[j] ^ 1) == rec[j + 1];
+            if (taut) continue;
             rec[0] = (int32_t)((uint32_t)sz | ((uint32_t)std::min<int32_t>(lbd, 255) << 6) | (MS_FOREIGN_PRODUCER << 14));
             for (int j = sz + 1; j < MS_SHARE_REC; j++) rec[j] = 0;
             recs.insert(recs.end(), rec, rec + MS_SHARE_REC);
