@@ -1,7 +1,8 @@
 """The C ABI's contract at its edges, on the CPU through the wavefront emulator build of the solver (tests/emu): which
 return code and which mi355sat_last_error text every refused call gets, what a refused call still does (assumptions
 consumed, a core's length reported), that the timed entry points add to stats.solve_seconds, what core minimisation
-leaves in stats, and the calls after which a warm incremental solve has to start cold.
+leaves in stats, the calls after which a warm incremental solve has to start cold, and what the proof check / trim entries
+refuse, with which text, and whether an earlier trim's result survives the refusal.
 
 One 3-variable formula throughout, (1 | 2) & (-1 | 3) & (-2 | 3): satisfiable, 3 is implied, UNSAT under [-3] and under
 [-1, -2], where both assumptions are needed."""
@@ -238,4 +239,159 @@ def test_what_makes_the_next_warm_solve_start_cold(between, reason):
     else:
         assert (d["cold_solves"], d["warm_solves"], d["last_cold_reason"]) == (2, 0, reason)
     assert s.solve() == SolverResult.Sat and s.debug_incremental()["warm_solves"] == (2 if between is None else 1)
+    s.close()
+
+
+# ---- proof check and trim (mi355sat_check_proof / _trim_proof and their _file variants) ----------------------------------
+# Clause (3) is RUP from the formula with an empty proof: trim_proof([], target=(3,)) is the smallest valid trim, its core
+# all three clauses, no lemma needed.
+DEL = -2 ** 31
+PROOF_ENTRIES = ["check_proof", "check_proof_file", "trim_proof", "trim_proof_file"]
+NO_TRIM = "no trimmed proof: the last call was not a mi355sat_trim_proof() that found the proof valid"
+
+
+def drup_text(words):
+    return "".join("d " if w == DEL else ("0\n" if w == 0 else f"{w} ") for w in words)
+
+
+def proof_entry(s, entry, tmp_path):
+    """(call(words, target=()), the entry's name in its messages); a _file variant gets the words as DRUP text."""
+    fn, name = getattr(s, entry), entry.replace("_file", "")
+    if not entry.endswith("_file"):
+        return (lambda words, target=(): fn(words, target=target)), name
+
+    def call(words, target=()):
+        path = tmp_path / "proof.drup"
+        path.write_text(drup_text(words))
+        return fn(path, target=target)
+    return call, name
+
+
+def valid_trim(s):
+    res = s.trim_proof([], target=(3,))
+    assert res["check"]["valid"] == 1 and res["core"] == [0, 1, 2] and res["lemmas"] == []
+    assert s.trim_core() == [0, 1, 2]
+
+
+def trim_getters_refuse(s, tmp_path):
+    refused(s, ERR_STATE, NO_TRIM, s.trim_core)
+    refused(s, ERR_STATE, NO_TRIM, s.trim_lemmas)
+    refused(s, ERR_STATE, NO_TRIM, s.trim_write_drup, tmp_path / "t.drup")
+    refused(s, ERR_STATE, NO_TRIM, s.trim_write_lrat, tmp_path / "t.lrat")
+    assert not (tmp_path / "t.drup").exists() and not (tmp_path / "t.lrat").exists()
+
+
+def test_proof_entries_refuse_null_arguments_and_unknown_flags_and_leave_the_trim_result(tmp_path):
+    from timberborn_support_solver_amd.solver import Mi355SatProofInfo, Mi355SatTrimInfo
+    s = solver()
+    L, h = s._L, s._h
+    valid_trim(s)
+    pi, ti = Mi355SatProofInfo(), Mi355SatTrimInfo()
+    one, path = i32([3]), str(tmp_path / "proof.drup").encode()
+    (tmp_path / "proof.drup").write_text("")
+    for args in [(None, None, 0, ptr(one), 1, 0, pi), (h, None, 0, ptr(one), 1, 0, None), (h, None, 1, ptr(one), 1, 0, pi),
+                 (h, None, 0, None, 1, 0, pi)]:
+        assert L.mi355sat_check_proof(*args) == ERR_ARG, args
+    for args in [(None, path, ptr(one), 1, 0, pi), (h, path, ptr(one), 1, 0, None), (h, None, ptr(one), 1, 0, pi),
+                 (h, path, None, 1, 0, pi)]:
+        assert L.mi355sat_check_proof_file(*args) == ERR_ARG, args
+    for args in [(None, None, 0, ptr(one), 1, 0, 0, ti), (h, None, 0, ptr(one), 1, 0, 0, None), (h, None, 1, ptr(one), 1, 0, 0, ti),
+                 (h, None, 0, None, 1, 0, 0, ti), (h, None, 0, ptr(one), 1, 0, 2, ti), (h, None, 0, ptr(one), 1, 0, 3, ti)]:
+        assert L.mi355sat_trim_proof(*args) == ERR_ARG, args
+    for args in [(None, path, ptr(one), 1, 0, 0, ti), (h, path, ptr(one), 1, 0, 0, None), (h, None, ptr(one), 1, 0, 0, ti),
+                 (h, path, None, 1, 0, 0, ti), (h, path, ptr(one), 1, 0, 2, ti)]:
+        assert L.mi355sat_trim_proof_file(*args) == ERR_ARG, args
+    assert s.trim_core() == [0, 1, 2]
+    s.close()
+
+
+@pytest.mark.parametrize("entry", PROOF_ENTRIES)
+def test_proof_entry_refusals_have_their_texts_and_leave_the_trim_result(entry, tmp_path):
+    s = solver()
+    call, name = proof_entry(s, entry, tmp_path)
+    valid_trim(s)
+    # a proof that does not parse
+    refused(s, ERR_ARG, "proof: a variable the handle does not have", call, [4, 0], (3,))
+    assert s.trim_core() == [0, 1, 2]
+    refused(s, ERR_ARG, "proof: the last clause is not terminated", call, [3, 0, 1, 2], (3,))
+    assert s.trim_core() == [0, 1, 2]
+    if not entry.endswith("_file"):                 # (in a file a "d" inside a clause is no number: malformed, below)
+        refused(s, ERR_ARG, "proof: a deletion marker inside a clause", call, [1, DEL, 2, 0], (3,))
+        assert s.trim_core() == [0, 1, 2]
+    # a bad target: refused after the earlier result was dropped
+    refused(s, ERR_ARG, "proof target: literal 0 inside a clause", call, [], (1, 0, 2))
+    trim_getters_refuse(s, tmp_path)
+    valid_trim(s)
+    refused(s, ERR_ARG, "proof target: literal 0 inside a clause", call, [], (1, DEL))
+    trim_getters_refuse(s, tmp_path)
+    valid_trim(s)
+    refused(s, ERR_ARG, "proof target: a variable the handle does not have", call, [3, 0], (4,))
+    trim_getters_refuse(s, tmp_path)
+    # during a sweep (sweep_begin dropped the result already)
+    valid_trim(s)
+    s.sweep_begin([[-3], [3]])
+    refused(s, ERR_STATE, f"{name}() called during a sweep", call, [], (3,))
+    trim_getters_refuse(s, tmp_path)
+    s.sweep_end()
+    valid_trim(s)
+    # inside an unterminated clause
+    assert s._L.mi355sat_add(s._h, 1) == 0
+    refused(s, ERR_STATE, f"{name}() called inside an unterminated clause", call, [], (3,))
+    assert s.trim_core() == [0, 1, 2]
+    assert s._L.mi355sat_add(s._h, 0) == 0          # (the clause added drops the result)
+    trim_getters_refuse(s, tmp_path)
+    s.close()
+
+
+@pytest.mark.parametrize("entry", ["check_proof_file", "trim_proof_file"])
+def test_proof_file_entries_refuse_a_missing_and_a_malformed_file(entry, tmp_path):
+    s = solver()
+    valid_trim(s)
+    fn = getattr(s, entry)
+    missing = tmp_path / "none.drup"
+    refused(s, ERR_ARG, "cannot open proof file " + str(missing), fn, missing, (3,))
+    for text in ["1 x 0\n", "2147483648 0\n", "-2147483648 0\n", "1 d 2 0\n"]:
+        bad = tmp_path / "bad.drup"
+        bad.write_text(text)
+        refused(s, ERR_ARG, "malformed proof file " + str(bad), fn, bad, (3,))
+        assert s.trim_core() == [0, 1, 2]
+    (tmp_path / "ok.drup").write_text("d 1 2 0\n3 0\n")
+    res = fn(tmp_path / "ok.drup", (3,))
+    res = res.get("check", res)
+    assert res["valid"] == 1 and res["n_lemmas"] == 1 and res["n_deletions_ignored"] == 1
+    s.close()
+
+
+def test_trim_readers_and_writers_refuse_with_their_texts(tmp_path):
+    s = solver()
+    trim_getters_refuse(s, tmp_path)                # before any trim
+    assert s.trim_proof([1, 0], target=(3,))["check"]["valid"] == 0        # (1) is not RUP: no result either
+    trim_getters_refuse(s, tmp_path)
+    valid_trim(s)
+    buf, n = u64([7, 7, 7]), ctypes.c_uint64(0)
+    assert s._L.mi355sat_trim_core(s._h, ptr(buf), 2, ctypes.byref(n)) == ERR_ARG
+    assert err(s) == "index buffer too small" and n.value == 3 and list(buf) == [7, 7, 7]
+    refused(s, ERR_STATE, "trim_write_lrat(): the proof was trimmed without MI355SAT_TRIM_HINTS", s.trim_write_lrat, tmp_path / "t.lrat")
+    assert not (tmp_path / "t.lrat").exists()
+    for write in (s.trim_write_drup, s.trim_write_lrat):
+        unwritable = tmp_path / "no_such_dir" / "t.out"
+        if write == s.trim_write_lrat:
+            assert s.trim_proof([], target=(3,), hints=True)["core"] == [0, 1, 2]
+        refused(s, ERR_ARG, "cannot open " + str(unwritable), write, unwritable)
+        assert not unwritable.exists() and s.trim_core() == [0, 1, 2]
+    s.trim_write_lrat(tmp_path / "t.lrat")
+    line = (tmp_path / "t.lrat").read_text().split()           # one line, the target's: id 4, (3), the three clauses as hints
+    assert line[:3] == ["4", "3", "0"] and sorted(line[3:-1]) == ["1", "2", "3"] and line[-1] == "0"
+    s.close()
+
+
+def test_check_proof_and_trim_proof_are_timed_and_count_their_launches():
+    s = solver()
+    for call in (lambda: s.check_proof([], target=(3,)), lambda: s.trim_proof([], target=(3,))["check"]):
+        before = s.stats()
+        info = call()
+        after = s.stats()
+        assert info["valid"] == 1 and info["launches"] >= 1
+        assert after["solve_seconds"] > before["solve_seconds"]
+        assert after["kernel_launches"] == before["kernel_launches"] + info["launches"]
     s.close()

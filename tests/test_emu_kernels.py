@@ -2,6 +2,7 @@
 against tests/emu (a 64-lane fiber emulator; see tests/emu/hip_shim.h) and driven through the
 same C ABI.  Parity with the oracle on small cases; the GPU tests are the authority for the
 real machine."""
+import re
 import threading
 import time
 
@@ -301,6 +302,33 @@ def test_emulated_sweep_moves_workers_to_open_instances_and_drops_implied_ones()
     check_sat_answer(cnf, s.solution_of(i4, cnf.n_vars), enc, grid, 4)
     for i, k in enumerate(ks):                          # whatever else was decided is consistent with k* = 4
         assert res[i] in (SolverResult.Interrupted, SolverResult.Sat if k >= 4 else SolverResult.Unsat)
+    s.close()
+
+
+def test_emulated_sweep_without_rebalancing_parks_the_worker_of_a_withdrawn_bound(capfd):
+    """opts.rebalance < 0: the worker of a withdrawn bound is parked instead of moved (the park record of rebalance_workers,
+    which nothing else on the CPU reaches).  Every other bound is decided by its own worker, the withdrawn one stays open.
+    The solver's verbose line counts the busy workers after every slice: all but the parked one and those that refuted
+    their bound (a worker that found a model stays busy, and without rebalancing none takes up another bound)."""
+    grid = make_grid("rect8x8")
+    enc = Encoding.encode(platform_defs("1x1"), grid)
+    cnf = enc.with_limits_into_cnf(PlatformLimits({(1, 1): 8}), sweep=True)
+    ks = [8, 5, 4, 3, 2]                                                       # k* = 4
+    sets = [[-int(cnf.card_outputs[k])] if k < 8 else [] for k in ks]
+    s = emu_solver(workers=5, slice_conflicts=20, rebalance=-1, verbose=1)
+    s.add_cnf(cnf.lits, cnf.offsets)
+    s.sweep_begin(sets)
+    s.sweep_drop([ks.index(5)])                     # every worker is running: the one of k = 5 is parked
+    capfd.readouterr()
+    for _ in range(400):
+        res, nd = s.sweep_step()
+        busy = re.findall(r"busy=(\d+)/5 ", capfd.readouterr().err)
+        assert busy == [str(5 - 1 - res.count(SolverResult.Unsat))]
+        if nd == len(ks):
+            break
+    assert res == [SolverResult.Sat, SolverResult.Interrupted, SolverResult.Sat, SolverResult.Unsat, SolverResult.Unsat]
+    s.sweep_end()
+    check_sat_answer(cnf, s.solution_of(ks.index(4), cnf.n_vars), enc, grid, 4)
     s.close()
 
 

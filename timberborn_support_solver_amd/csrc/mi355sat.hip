@@ -20,6 +20,7 @@
 #include <mutex>
 #include <queue>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -275,6 +276,9 @@ struct DevBuf {
         alloc(v.size());
         if (!v.empty()) HIPCHK(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
     }
+    void upload_nonempty(const std::vector<T>& v, hipStream_t s) {   // an empty list as one zero element: the buffer has an address
+        upload(v.empty() ? std::vector<T>(1) : v, s);
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -496,9 +500,17 @@ struct Prepared {
 
 inline uint64_t var_of(int32_t d) { return (uint64_t)(d < 0 ? -(int64_t)d : d); }      // |d|: a DIMACS literal's variable
 inline int32_t to_internal(int32_t d) { return d > 0 ? 2 * (d - 1) : 2 * (-d - 1) + 1; }
+inline int32_t to_dimacs(int32_t l) { return (l & 1) ? -((l >> 1) + 1) : ((l >> 1) + 1); }      // and back
 inline int32_t to_device(const std::vector<uint32_t>& perm, int32_t d) {   // DIMACS literal -> device literal
     return d > 0 ? 2 * (int32_t)perm[d - 1] : 2 * (int32_t)perm[-d - 1] + 1;
 }
+inline std::vector<uint32_t> inverse_order(const std::vector<uint32_t>& perm) {   // device variable -> caller's (0-based)
+    std::vector<uint32_t> inv(perm.size());
+    for (uint32_t e = 0; e < perm.size(); e++) inv[perm[e]] = e;
+    return inv;
+}
+// A device literal as the caller's DIMACS literal, through the inverse of the device's variable order (inverse_order(perm)).
+inline int32_t to_dimacs(const std::vector<uint32_t>& inv, int32_t l) { return to_dimacs(2 * (int32_t)inv[l >> 1] | (l & 1)); }
 // The same for a formula that went through the simplification - the one route of assumptions, clauses attached warm, phase
 // hints and imported records: the equivalent-literal substitution (which may flip the sign), then the device's variable
 // order (perm: s.perm once uploaded).  The caller has checked the range.  gone (may be null), per caller variable: resolved
@@ -936,9 +948,9 @@ void upload_formula(mi355sat& s, const Prepared& P, uint32_t assump_cap, uint32_
     s.n_vars = P.n_vars;
     s.perm = P.perm;
     s.d_cl_lits.upload(P.cl_lits, s.stream);
-    s.d_bin_lits.upload(P.bin_lits.empty() ? std::vector<int32_t>{0} : P.bin_lits, s.stream);
-    s.d_tern_pairs.upload(P.tern_pairs.empty() ? std::vector<ms_int2>{ms_int2{0, 0}} : P.tern_pairs, s.stream);
-    s.d_tern_owner.upload(P.tern_owner.empty() ? std::vector<int32_t>{0} : P.tern_owner, s.stream);
+    s.d_bin_lits.upload_nonempty(P.bin_lits, s.stream);
+    s.d_tern_pairs.upload_nonempty(P.tern_pairs, s.stream);
+    s.d_tern_owner.upload_nonempty(P.tern_owner, s.stream);
     s.sh.n_vars = P.n_vars;
     s.sh.n_orig = (uint32_t)P.cl_hdr.size();
     s.sh.cl_lits = s.d_cl_lits.p;
@@ -1014,11 +1026,11 @@ void customize(mi355sat& s, const std::vector<int32_t>* assump, const std::vecto
                const std::vector<int32_t>* script, const std::vector<uint64_t>* script_off, uint32_t n_instances,
                int32_t park_from = -1) {
     if (assump_off) {
-        s.d_assump.upload(assump->empty() ? std::vector<int32_t>{0} : *assump, s.stream);
+        s.d_assump.upload_nonempty(*assump, s.stream);
         s.d_assump_off.upload(*assump_off, s.stream);
     }
     if (script_off) {
-        s.d_script.upload(script->empty() ? std::vector<int32_t>{0} : *script, s.stream);
+        s.d_script.upload_nonempty(*script, s.stream);
         s.d_script_off.upload(*script_off, s.stream);
     }
     hipLaunchKernelGGL(ms_customize_kernel, dim3(s.n_alloc), dim3(256), 0, s.stream, s.L, s.d_slabs.p,
@@ -1680,6 +1692,31 @@ inline mi355sat_search_build choose_build(uint32_t active, uint32_t lds_val_byte
     return b;
 }
 
+// One timed kernel launch on the stream: `launch` between two events, its error checked, the time between the events added
+// to stats.kernel_seconds, stats.kernel_launches counted.  `after` is queued behind the second event and ahead of the wait:
+// what it launches is not measured.
+template <class Launch, class After>
+SliceResult timed_launch(mi355sat& s, Launch launch, After after) {
+    HIPCHK(hipEventRecord(s.ev0, s.stream));
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s.ev1, s.stream));
+    after();
+    HIPCHK(hipEventSynchronize(s.ev1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+    s.stats.kernel_seconds += ms * 1e-3;
+    s.stats.kernel_launches++;
+    return SliceResult{ms};
+}
+
+// A flag known at run time as a template argument of a launch: f(std::true_type) or f(std::false_type).
+template <class F>
+void with_flag(bool flag, F f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_refuted = true, uint32_t active = 0, int auto_slice_ms = 20) {
     if (active == 0 || active > s.n_alloc) active = s.n_alloc;   // workers [0, active) run this slice
     MsParams prm{};
@@ -1718,36 +1755,27 @@ SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_r
     }
     const mi355sat_search_build build = choose_build(active, s.lds_val_bytes, s.lds_val, s.opts.lds_val, s.opts.one_per_simd, mode);
     const bool lds = build.lds != 0;
-    const uint32_t dyn = build.dyn_lds_bytes;
-    HIPCHK(hipEventRecord(s.ev0, s.stream));
-    if (mode == 0) {
-        const int wps = build.wps;
-        const uint64_t n_launches = s.last_build.launches;
-        const uint32_t seen = s.last_build.builds_seen;
-        s.last_build = build;
-        s.last_build.launches = n_launches + 1;
-        s.last_build.builds_seen = seen | (1u << ((lds ? 3 : 0) + (wps == 1 ? 0 : (wps == 2 ? 1 : 2))));
-#define MS_LAUNCH_SEARCH(LVV, W) hipLaunchKernelGGL((ms_search_kernel<LVV, W>), dim3(active), dim3(MS_WAVE), (LVV) ? dyn : 0, s.stream, s.sh, s.L, s.d_slabs.p, prm)
-        if (lds) {
-            if (wps == 1) MS_LAUNCH_SEARCH(true, 1);
-            else if (wps == 2) MS_LAUNCH_SEARCH(true, 2);
-            else MS_LAUNCH_SEARCH(true, MS_SEARCH_WAVES_PER_SIMD);
-        } else {
-            if (wps == 1) MS_LAUNCH_SEARCH(false, 1);
-            else if (wps == 2) MS_LAUNCH_SEARCH(false, 2);
-            else MS_LAUNCH_SEARCH(false, MS_SEARCH_WAVES_PER_SIMD);
+    const int wps = build.wps;
+    return timed_launch(s, [&] {
+        if (mode == 0) {
+            const uint64_t n_launches = s.last_build.launches;
+            const uint32_t seen = s.last_build.builds_seen;
+            s.last_build = build;
+            s.last_build.launches = n_launches + 1;
+            s.last_build.builds_seen = seen | (1u << ((lds ? 3 : 0) + (wps == 1 ? 0 : (wps == 2 ? 1 : 2))));
         }
-#undef MS_LAUNCH_SEARCH
-    } else if (mode == 2) {
-        if (lds) hipLaunchKernelGGL(ms_probe_kernel<true>, dim3(active), dim3(MS_WAVE), dyn, s.stream, s.sh, s.L, s.d_slabs.p, prm);
-        else hipLaunchKernelGGL(ms_probe_kernel<false>, dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm);
-    } else {
-        if (lds) hipLaunchKernelGGL(ms_bcp_kernel<true>, dim3(active), dim3(MS_WAVE), dyn, s.stream, s.sh, s.L, s.d_slabs.p, prm);
-        else hipLaunchKernelGGL(ms_bcp_kernel<false>, dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s.ev1, s.stream));
-    if (share) {
+        with_flag(lds, [&](auto lds_build) {      // (dyn_lds_bytes is 0 in the builds without the assignment in LDS)
+            constexpr bool LV = decltype(lds_build)::value;
+#define MS_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm)
+            if (mode == 2) MS_LAUNCH(ms_probe_kernel<LV>);
+            else if (mode != 0) MS_LAUNCH(ms_bcp_kernel<LV>);
+            else if (wps == 1) MS_LAUNCH(ms_search_kernel<LV, 1>);
+            else if (wps == 2) MS_LAUNCH(ms_search_kernel<LV, 2>);
+            else MS_LAUNCH(ms_search_kernel<LV, MS_SEARCH_WAVES_PER_SIMD>);
+#undef MS_LAUNCH
+        });
+    }, [&] {
+        if (!share) return;      // the slice's exported clauses into the ring, behind the measured launch
         if ((++s.share_slices & 255) == 0)   // forget old signatures before the set fills up (a clause may then be passed on twice)
             HIPCHK(hipMemsetAsync(s.d_share_hash.p, 0, sizeof(unsigned long long) * s.share_hash_n, s.stream));
         HIPCHK(hipMemsetAsync(s.d_share_intake.p, 0, sizeof(uint32_t), s.stream));
@@ -1756,13 +1784,7 @@ SliceResult launch_slice(mi355sat& s, int mode, bool stop_on_any, bool done_on_r
                            s.n_alloc, s.d_share_pool.p, s.share_slots, s.d_share_n.p, s.d_share_hash.p, s.share_hash_n - 1,
                            s.d_share_intake.p, share_intake_cap, ordered ? 1 : 0);
         HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventSynchronize(s.ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-    s.stats.kernel_seconds += ms * 1e-3;
-    s.stats.kernel_launches++;
-    return SliceResult{ms};
+    });
 }
 
 void launch_probe(mi355sat& s) { launch_slice(s, 2, false); }
@@ -1776,7 +1798,7 @@ void proof_open(mi355sat& s) {
     if (!s.proof_file) throw HipErr{"cannot open proof file " + s.proof_path};
     for (int32_t l : s.simp_proof) {   // (caller's numbering already)
         if (l < 0) fputs("0\n", s.proof_file);
-        else fprintf(s.proof_file, "%d ", (l & 1) ? -((l >> 1) + 1) : ((l >> 1) + 1));
+        else fprintf(s.proof_file, "%d ", to_dimacs(l));
     }
 }
 void proof_drain(mi355sat& s) {
@@ -1784,8 +1806,7 @@ void proof_drain(mi355sat& s) {
     const uint32_t W = (uint32_t)(s.d_proof_len.n / 2);     // per worker: lemma words from word 0 up, deletion words from the top down
     std::vector<uint32_t> len(2 * (size_t)W);
     HIPCHK(hipMemcpy(len.data(), s.d_proof_len.p, sizeof(uint32_t) * 2 * W, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> inv(s.perm.size());
-    for (uint32_t e = 0; e < s.perm.size(); e++) inv[s.perm[e]] = e;
+    const std::vector<uint32_t> inv = inverse_order(s.perm);
     std::vector<int32_t> buf;
     bool any = false;
     for (uint32_t w = 0; w < W; w++) {
@@ -1800,7 +1821,7 @@ void proof_drain(mi355sat& s) {
         for (uint32_t i = 0; i < buf.size(); i++) {
             if (buf[i] == -2) fputs("d ", s.proof_file);       // deletion line
             else if (buf[i] < 0) fputs("0\n", s.proof_file);
-            else fprintf(s.proof_file, "%d ", (buf[i] & 1) ? -((int)inv[buf[i] >> 1] + 1) : ((int)inv[buf[i] >> 1] + 1));
+            else fprintf(s.proof_file, "%d ", to_dimacs(inv, buf[i]));
         }
     }
     if (any) { HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * W, s.stream)); HIPCHK(hipStreamSynchronize(s.stream)); }
@@ -1824,6 +1845,13 @@ const char* status_text(int st) {
         case MS_ST_ERR_INTERNAL: return "device solver internal error";
         default: return "unknown device status";
     }
+}
+
+// A worker's negative status as its call's failure: the text in s.err, the code `internal` (each caller's own) for
+// MS_ST_ERR_INTERNAL and MI355SAT_ERR_OOM for a full store.  (warm_begin answers a full store with a cold start: not here.)
+int status_error(mi355sat& s, int st, int internal, const char* prefix = "") {
+    s.err = std::string(prefix) + status_text(st);
+    return st == MS_ST_ERR_INTERNAL ? internal : MI355SAT_ERR_OOM;
 }
 
 // Shared driver for solve(), solve_batch() and the stepwise sweep API.
@@ -1910,6 +1938,32 @@ struct Sweep {
             w_cube[w].assign(base_assump.begin() + base_off[inst], base_assump.begin() + base_off[inst + 1]);
             open[inst]++;
         }
+    }
+};
+
+// What the host tells workers between two slices, for ms_assign_kernel to apply: a new status, a restart request and a
+// new assumption list (the worker's cube) each.
+struct WorkerUpdates {
+    std::vector<int32_t> upd, data;
+    // The record as ms_assign_kernel reads it, five words: worker, status, restart request, the length of its assumption
+    // list and where that starts in the launch's data buffer.
+    void add_at(uint32_t w, int32_t status, int32_t restart, size_t n, size_t at) {
+        upd.insert(upd.end(), {(int32_t)w, status, restart, (int32_t)n, (int32_t)at});
+    }
+    void add(uint32_t w, int32_t status, int32_t restart, const std::vector<int32_t>& cube) {   // the list travels in `data`
+        add_at(w, status, restart, cube.size(), data.size());
+        data.insert(data.end(), cube.begin(), cube.end());
+    }
+    // Nothing to tell: no upload, no launch.  resident (warm_begin, its one user): the lists are on the device already and
+    // more follows on the stream - no `data`, no wait.
+    void send(mi355sat& s, Sweep& sw, const int32_t* resident = nullptr) {
+        if (upd.empty()) return;
+        const uint32_t n = (uint32_t)(upd.size() / 5);
+        sw.d_upd.upload(upd, s.stream);
+        if (!resident) sw.d_data.upload_nonempty(data, s.stream);
+        hipLaunchKernelGGL(ms_assign_kernel, dim3(n), dim3(64), 0, s.stream, s.L, s.d_slabs.p, n, sw.d_upd.p, resident ? resident : sw.d_data.p);
+        HIPCHK(hipGetLastError());
+        if (!resident) HIPCHK(hipStreamSynchronize(s.stream));
     }
 };
 
@@ -2039,17 +2093,13 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
 // cubes are closed.
 void schedule_cubes(mi355sat& s, Sweep& sw) {
     const uint32_t W = s.n_workers, cap = s.L.assump_cap;
-    std::vector<int32_t> upd, data;
-    auto push_update = [&](uint32_t w, int32_t status, int32_t restart) {
-        upd.insert(upd.end(), {(int32_t)w, status, restart, (int32_t)sw.w_cube[w].size(), (int32_t)data.size()});
-        data.insert(data.end(), sw.w_cube[w].begin(), sw.w_cube[w].end());
-    };
+    WorkerUpdates u;
     std::vector<uint32_t> idle, victims;
     for (uint32_t w = 0; w < W; w++) {
         const bool undecided = sw.results[sw.w_inst[w]] == MI355SAT_INTERRUPTED;
         if (sw.w_busy[w] && !undecided) {   // its instance was decided by someone else: park it
             sw.w_busy[w] = 0;
-            if (sw.sts[w].status == MS_ST_RUNNING) { sw.w_cube[w].clear(); push_update(w, MS_ST_PARKED, 0); sw.sts[w].status = MS_ST_PARKED; }
+            if (sw.sts[w].status == MS_ST_RUNNING) { sw.w_cube[w].clear(); u.add(w, MS_ST_PARKED, 0, sw.w_cube[w]); sw.sts[w].status = MS_ST_PARKED; }
         }
         if (!sw.w_busy[w]) idle.push_back(w);
         else if (sw.sts[w].status == MS_ST_RUNNING && sw.sts[w].n_split > 0) victims.push_back(w);
@@ -2077,20 +2127,14 @@ void schedule_cubes(mi355sat& s, Sweep& sw) {
             sw.open[sw.w_inst[v]]++;
             sw.n_splits++;
             taken[v] = round + 1;
-            push_update(t, MS_ST_RUNNING, 1);
+            u.add(t, MS_ST_RUNNING, 1, sw.w_cube[t]);
             any = true;
         }
         if (!any) break;
     }
     for (uint32_t v : victims)
-        if (taken[v]) push_update(v, MS_ST_RUNNING, 0);
-    if (upd.empty()) return;
-    sw.d_upd.upload(upd, s.stream);
-    sw.d_data.upload(data.empty() ? std::vector<int32_t>{0} : data, s.stream);
-    hipLaunchKernelGGL(ms_assign_kernel, dim3((uint32_t)(upd.size() / 5)), dim3(64), 0, s.stream, s.L, s.d_slabs.p,
-                       (uint32_t)(upd.size() / 5), sw.d_upd.p, sw.d_data.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s.stream));
+        if (taken[v]) u.add(v, MS_ST_RUNNING, 0, sw.w_cube[v]);
+    u.send(s, sw);
 }
 
 inline bool inst_open(const Sweep& sw, uint32_t inst) { return sw.results[inst] == MI355SAT_INTERRUPTED && !sw.dropped[inst]; }
@@ -2111,10 +2155,10 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
     }
     std::vector<uint32_t> open;
     for (uint32_t i = 0; i < n_instances; i++) if (inst_open(sw, i)) open.push_back(i);
-    std::vector<int32_t> upd, data;
+    WorkerUpdates u;
     auto park = [&](uint32_t w) {
         if (sw.sts[w].status != MS_ST_RUNNING) return;
-        upd.insert(upd.end(), {(int32_t)w, MS_ST_PARKED, 0, 0, (int32_t)data.size()});
+        u.add(w, MS_ST_PARKED, 0, {});
         sw.sts[w].status = MS_ST_PARKED;
         sw.w_busy[w] = 0;
     };
@@ -2163,19 +2207,12 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
             sw.w_inst[w] = (int32_t)best;
             sw.w_busy[w] = 1;
             sw.w_cube[w].assign(sw.base_assump.begin() + sw.base_off[best], sw.base_assump.begin() + sw.base_off[best + 1]);
-            upd.insert(upd.end(), {(int32_t)w, MS_ST_RUNNING, 1, (int32_t)sw.w_cube[w].size(), (int32_t)data.size()});
-            data.insert(data.end(), sw.w_cube[w].begin(), sw.w_cube[w].end());
+            u.add(w, MS_ST_RUNNING, 1, sw.w_cube[w]);
             sw.sts[w].status = MS_ST_RUNNING;
             sw.n_moved++;
         }
     }
-    if (upd.empty()) return;
-    sw.d_upd.upload(upd, s.stream);
-    sw.d_data.upload(data.empty() ? std::vector<int32_t>{0} : data, s.stream);
-    hipLaunchKernelGGL(ms_assign_kernel, dim3((uint32_t)(upd.size() / 5)), dim3(64), 0, s.stream, s.L, s.d_slabs.p,
-                       (uint32_t)(upd.size() / 5), sw.d_upd.p, sw.d_data.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s.stream));
+    u.send(s, sw);
 }
 
 // What ms_final_kernel and ms_core_model_kernel answer with: per wave k of n a row of bits (sw.d_fout, out_words words each:
@@ -2316,14 +2353,12 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
         return MI355SAT_COLD_NONE;
     }
     // the assumption list: to every resident worker now, and where grow_workers takes it from for the workers it creates
-    s.d_assump.upload(a_int.empty() ? std::vector<int32_t>{0} : a_int, s.stream);
+    s.d_assump.upload_nonempty(a_int, s.stream);
     s.d_assump_off.upload(a_off, s.stream);
-    std::vector<int32_t> upd;
-    for (uint32_t w = 0; w < s.n_alloc; w++) upd.insert(upd.end(), {(int32_t)w, MS_ST_RUNNING, 1, (int32_t)a_int.size(), 0});
-    sw.d_upd.upload(upd, s.stream);
-    hipLaunchKernelGGL(ms_assign_kernel, dim3(s.n_alloc), dim3(64), 0, s.stream, s.L, s.d_slabs.p, s.n_alloc, sw.d_upd.p, s.d_assump.p);
-    HIPCHK(hipGetLastError());
-    s.d_inc_lits.upload(I.lits.empty() ? std::vector<int32_t>{0} : I.lits, s.stream);
+    WorkerUpdates u;
+    for (uint32_t w = 0; w < s.n_alloc; w++) u.add_at(w, MS_ST_RUNNING, 1, a_int.size(), 0);    // (every worker reads s.d_assump)
+    u.send(s, sw, s.d_assump.p);
+    s.d_inc_lits.upload_nonempty(I.lits, s.stream);
     s.d_inc_offs.upload(I.offs, s.stream);
     attach_clauses(s, 0, s.n_alloc, c0, c1);    // (without new clauses it still takes every worker to level 0)
     HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
@@ -2384,10 +2419,7 @@ int sweep_step(mi355sat& s, Sweep& sw) {
     for (uint32_t w = 0; w < s.n_workers; w++) {
         const MsState& st = sw.sts[w];
         confl += st.conflicts;
-        if (st.status < 0) {
-            set_error(&s, status_text(st.status));
-            rc = st.status == MS_ST_ERR_INTERNAL ? MI355SAT_ERR_STATE : MI355SAT_ERR_OOM;
-        }
+        if (st.status < 0) rc = status_error(s, st.status, MI355SAT_ERR_STATE);
         if (!sw.w_busy[w]) continue;
         const uint32_t inst = (uint32_t)sw.w_inst[w];
         if (st.status == MS_ST_REFUTED || st.status == MS_ST_UNSAT) {   // this worker's cube is closed
@@ -2559,7 +2591,7 @@ void sweep_repose(mi355sat& s, Sweep& sw, uint32_t inst, const std::vector<int32
 void sweep_retarget(mi355sat& s, Sweep& sw) {
     sw.decided = 0;
     for (uint32_t i = 0; i < sw.n_instances; i++) sw.decided += inst_open(sw, i) ? 0 : 1;
-    s.d_assump.upload(sw.base_assump.empty() ? std::vector<int32_t>{0} : sw.base_assump, s.stream);
+    s.d_assump.upload_nonempty(sw.base_assump, s.stream);
     s.d_assump_off.upload(sw.base_off, s.stream);
     if (sw.sts.size() != s.n_workers) gather_states(s, sw.sts);
     rebalance_workers(s, sw, /*all=*/true);
@@ -2582,7 +2614,7 @@ int core_models(mi355sat& s, Sweep& sw, const std::vector<int32_t>& winners, con
     for (uint32_t k = 0; k < n; k++)
         if (q_off[k + 1] - q_off[k] > 32u * bit_row_words(s) || (uint32_t)winners[k] >= s.n_alloc) throw HipErr{"core minimisation: list out of range"};
     sw.d_fw.upload(winners, s.stream);
-    sw.d_qlits.upload(q.empty() ? std::vector<int32_t>{0} : q, s.stream);
+    sw.d_qlits.upload_nonempty(q, s.stream);
     sw.d_qoff.upload(q_off, s.stream);
     falsified.assign(n, {});
     return read_bit_rows(s, sw, n, "device solver internal error (a SAT worker's slab is no model)", [&](uint32_t out_words) {
@@ -2761,6 +2793,26 @@ struct ProofLemmas {
     uint64_t n_lemmas = 0, n_deletions = 0;
 };
 
+// One check as it passes from stage to stage of check_proof_impl.
+struct ProofCheck {
+    ProofLemmas& pf;                   // the proof; proof_target appends the target as item n_lemmas
+    mi355sat_proof_info& info;
+    uint32_t n_items = 0;              // the lemmas and the target
+    Prepared P;                        // the caller's clauses: not simplified, in the caller's variable order
+    // the proof as the device reads it (proof_device_form)
+    std::vector<int32_t> dl;           // device literals item by item, each variable at most once per item
+    std::vector<uint32_t> doff{0};
+    std::vector<uint8_t> skip;         // per item: it holds x and ~x - true whatever the assignment, never checked
+    uint64_t store_lits = 0;           // what the lemmas take in a worker's learnt store, each 16-byte aligned
+    // on the device (proof_upload): S segments of the item list, one worker each
+    uint32_t S = 0;
+    DevBuf<int32_t> d_lits;
+    DevBuf<uint32_t> d_offs;
+    DevBuf<uint8_t> d_skip;
+    DevBuf<unsigned long long> d_mins; // complements of the first failed lemma and of the point of refutation
+    bool interrupted = false;          // proof_launches stopped at the interrupt flag
+};
+
 // proof: flat words (mi355sat.h).  Returns 0 or MI355SAT_ERR_ARG with a text.
 int parse_proof_words(mi355sat& s, const int32_t* proof, uint64_t n_words, ProofLemmas& out) {
     uint64_t i = 0;
@@ -2811,8 +2863,9 @@ int read_proof_file(mi355sat& s, const char* path, std::vector<int32_t>& words) 
     return 0;
 }
 
-SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32_t* lits, const uint32_t* offs, const uint8_t* skip,
-                       uint32_t n_items, unsigned long long* mins, const MsTrace* trace = nullptr) {
+// One launch of the checker over all segments; mt.log set: the tracing build (a trim).
+SliceResult launch_rup(mi355sat& s, const ProofCheck& C, const MsTrace& mt) {
+    const uint32_t active = C.S, chunk = s.proof_chunk;
     MsParams prm{};
     prm.n_workers = active;
     prm.max_groups = s.opts.max_groups > 0 ? s.opts.max_groups : MS_MAX_GROUPS;
@@ -2820,21 +2873,15 @@ SliceResult launch_rup(mi355sat& s, uint32_t active, uint32_t chunk, const int32
     prm.slice_ticks = chunk ? 0 : 20ull * 100000ull;           // ... or 20 ms
     prm.stop_flag = s.stop_flag;
     const mi355sat_search_build build = choose_build(active, s.lds_val_bytes, s.lds_val, s.opts.lds_val, s.opts.one_per_simd, 1);
-    HIPCHK(hipEventRecord(s.ev0, s.stream));
-    const MsTrace none{};
-    if (trace) {
-        if (build.lds) hipLaunchKernelGGL((ms_rup_kernel<true, true>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, *trace);
-        else hipLaunchKernelGGL((ms_rup_kernel<false, true>), dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, *trace);
-    } else if (build.lds) hipLaunchKernelGGL((ms_rup_kernel<true, false>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, none);
-    else hipLaunchKernelGGL((ms_rup_kernel<false, false>), dim3(active), dim3(MS_WAVE), 0, s.stream, s.sh, s.L, s.d_slabs.p, prm, lits, offs, skip, n_items, mins, none);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s.ev1, s.stream));
-    HIPCHK(hipEventSynchronize(s.ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-    s.stats.kernel_seconds += ms * 1e-3;
-    s.stats.kernel_launches++;
-    return SliceResult{ms};
+    return timed_launch(s, [&] {
+        with_flag(build.lds != 0, [&](auto lds_build) {
+            with_flag(mt.log != nullptr, [&](auto traced) {
+                hipLaunchKernelGGL((ms_rup_kernel<decltype(lds_build)::value, decltype(traced)::value>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes,
+                                   s.stream, s.sh, s.L, s.d_slabs.p, prm, (const int32_t*)C.d_lits.p, (const uint32_t*)C.d_offs.p,
+                                   (const uint8_t*)C.d_skip.p, C.n_items, C.d_mins.p, mt);
+            });
+        });
+    }, [] {});
 }
 
 // ---- trimming a checked proof (mi355sat_trim_proof) -----------------------------------------------------------------------
@@ -2857,6 +2904,7 @@ struct TrimRun {
     std::map<uint64_t, Refutation> refuted;                       // by the item the worker stood in front of
     DevBuf<uint32_t> d_log, d_used;
     uint32_t words = 0;
+    MsTrace mt{};                      // what the tracing build of ms_rup_kernel gets (trim_begin)
 };
 
 static std::array<int32_t, 3> short_key(int32_t a, int32_t b, int32_t c) {
@@ -2865,9 +2913,10 @@ static std::array<int32_t, 3> short_key(int32_t a, int32_t b, int32_t c) {
     return k;
 }
 
-// The reverse maps, clause by clause as normalise sees them.  unsat_core: where normalise stops (an empty clause, or a
+// The reverse maps, clause by clause as normalise sees them.  Returns where normalise stops (an empty clause, or a
 // unit against an earlier unit), the clause or the pair that is - the whole core when the formula falls before any launch.
-void trim_maps(const mi355sat& s, TrimRun& T, std::vector<uint64_t>& unsat_core) {
+std::vector<uint64_t> trim_maps(const mi355sat& s, TrimRun& T) {
+    std::vector<uint64_t> unsat_core;
     std::vector<int32_t> tmp;
     T.n_clauses = s.offs.size() - 1;
     for (uint64_t c = 0; c < T.n_clauses; c++) {
@@ -2887,26 +2936,51 @@ void trim_maps(const mi355sat& s, TrimRun& T, std::vector<uint64_t>& unsat_core)
         else if (tmp.size() == 3) T.short_idx.emplace(short_key(tmp[0], tmp[1], tmp[2]), c);
         else T.long_idx.push_back(c);
     }
+    return unsat_core;
 }
 
-// Every worker's region of the dependency log after a launch: parsed, mapped, the cursors reset.
+int trim_fail(mi355sat& s, const char* what) {
+    s.err = std::string("proof trim: ") + what;
+    return MI355SAT_ERR_HIP;
+}
+
+// The dependency log's words per worker: the test hook's or the rule's, never below two items of the largest size - a worker
+// ends its launch when its region has less room than that.
+uint32_t trim_log_words(const mi355sat& s, uint32_t n_vars, uint32_t S) {
+    const uint64_t floor_words = 2 * MS_TR_ITEM_WORDS(n_vars);
+    const uint64_t rule = std::min<uint64_t>(1u << 18, (1u << 26) / S);
+    return (uint32_t)std::max<uint64_t>(floor_words, s.trim_log_words ? s.trim_log_words : rule);
+}
+
+// The trim before the launch: the reverse maps and the dependency log.
+void trim_begin(mi355sat& s, TrimRun& T, const ProofCheck& C) {
+    trim_maps(s, T);
+    T.words = trim_log_words(s, C.P.n_vars, C.S);
+    T.out->log_words_per_worker = T.words;
+    T.d_log.alloc((size_t)C.S * T.words);
+    T.d_used.upload(std::vector<uint32_t>(C.S, 0u), s.stream);
+    T.deps.assign(C.n_items, {});
+    T.have.assign(C.n_items, 0);
+    T.mt = MsTrace{T.d_log.p, T.d_used.p, T.words, 0};
+}
+
+// After every launch: each worker's region of the dependency log parsed and mapped, the cursors reset.
 int trim_drain(mi355sat& s, TrimRun& T, uint32_t S, uint32_t n_items) {
     std::vector<uint32_t> used(S), buf;
     HIPCHK(hipMemcpy(used.data(), T.d_used.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
     bool any = false;
     std::vector<std::array<int64_t, 3>> recs;        // pos, id, implied
-    auto fail = [&](const char* what) { s.err = std::string("proof trim: ") + what; return MI355SAT_ERR_HIP; };
     for (uint32_t w = 0; w < S; w++) {
         if (!used[w]) continue;
         any = true;
-        if (used[w] > T.words || used[w] % MS_TR_REC) return fail("a log cursor out of range");
+        if (used[w] > T.words || used[w] % MS_TR_REC) return trim_fail(s, "a log cursor out of range");
         buf.resize(used[w]);
         HIPCHK(hipMemcpy(buf.data(), T.d_log.p + (size_t)w * T.words, (size_t)used[w] * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < buf.size();) {
             const uint32_t item = buf[i] & ~MS_TR_REFUTED, n = buf[i + 1];
             const bool refuted = (buf[i] & MS_TR_REFUTED) != 0;
             if (item >= n_items + (refuted ? 1u : 0u) || (uint64_t)n > (uint64_t)s.L.n_vars + 2 || i + MS_TR_REC * ((size_t)n + 1) > buf.size())
-                return fail("a malformed log item");
+                return trim_fail(s, "a malformed log item");
             recs.clear();
             for (uint32_t r = 0; r < n; r++) {
                 const int32_t* x = (const int32_t*)&buf[i + MS_TR_REC * ((size_t)r + 1)];
@@ -2926,7 +3000,7 @@ int trim_drain(mi355sat& s, TrimRun& T, uint32_t S, uint32_t n_items) {
                     if ((uint32_t)x[1] < item) id = (int64_t)(T.n_clauses + (uint32_t)x[1]);
                     implied = x[3];
                 }
-                if (id < 0) return fail("a record names no clause of the caller and no earlier lemma");
+                if (id < 0) return trim_fail(s, "a record names no clause of the caller and no earlier lemma");
                 recs.push_back({pos, id, implied});
             }
             std::sort(recs.begin(), recs.end());
@@ -2953,35 +3027,58 @@ int trim_drain(mi355sat& s, TrimRun& T, uint32_t S, uint32_t n_items) {
     return 0;
 }
 
-// From the target backwards: a needed item's clauses enter the core, its lemmas become needed.  dl / doff / skip: the proof as
-// the device read it (the target's device literals decide which hints of a level-0 refutation a non-empty target keeps).
-int trim_reach(mi355sat& s, TrimRun& T, const ProofLemmas& pf, const std::vector<uint8_t>& skip, const std::vector<int32_t>& dl,
-               const std::vector<uint32_t>& doff, const mi355sat_proof_info& info) {
-    auto fail = [&](const char* what) { s.err = std::string("proof trim: ") + what; return MI355SAT_ERR_HIP; };
-    const uint64_t nl = pf.n_lemmas, nc = T.n_clauses;
-    std::vector<uint8_t> needed(nl, 0), core(nc, 0);
-    std::vector<uint64_t> target_ids;
+// The one way a trim result reaches the handle: the core, the needed lemmas (ascending), and as lines those lemmas and the
+// target, each (with hints) with the ids it rests on as LRAT numbers - a lemma's as traced, the target's given.
+void trim_publish(mi355sat& s, TrimRun& T, const ProofLemmas& pf, std::vector<uint64_t> core, std::vector<uint64_t> lemmas,
+                  const std::vector<uint64_t>& target_ids, bool no_lines) {
     mi355sat::Trim& R = s.trim;
     R.drop();
-    if (skip[nl]) R.no_lines = true;
-    else if (info.refuted_at != UINT64_MAX) {
-        auto it = T.refuted.find(info.refuted_at);
-        if (it == T.refuted.end()) return fail("no worker traced the refutation");
+    R.no_lines = no_lines;
+    R.n_clauses = T.n_clauses;
+    R.n_lemmas = pf.n_lemmas;
+    R.hints = (T.flags & MI355SAT_TRIM_HINTS) != 0;
+    std::sort(core.begin(), core.end());
+    R.core.swap(core);
+    R.lemmas.swap(lemmas);
+    auto line = [&](uint64_t j, const std::vector<uint64_t>& ids) {
+        R.lits.insert(R.lits.end(), pf.lits.begin() + pf.offs[j], pf.lits.begin() + pf.offs[j + 1]);
+        R.offs.push_back(R.lits.size());
+        if (!R.hints) return;
+        R.hint.emplace_back();
+        for (uint64_t id : ids) R.hint.back().push_back(id + 1);
+    };
+    for (uint64_t j : R.lemmas) line(j, T.deps[j]);
+    line(pf.n_lemmas, target_ids);
+    R.valid = true;
+    T.out->core_clauses = R.core.size();
+    T.out->lemmas_needed = R.lemmas.size();
+}
+
+// From the target backwards: a needed item's clauses enter the core, its lemmas become needed.  (The target's device
+// literals decide which hints of a level-0 refutation a non-empty target keeps.)
+int trim_reach(mi355sat& s, TrimRun& T, const ProofCheck& C) {
+    const uint64_t nl = C.pf.n_lemmas, nc = T.n_clauses, refuted_at = C.info.refuted_at;
+    const bool taut = C.skip[nl] != 0;           // a tautological target: nothing to derive, no lines
+    std::vector<uint8_t> needed(nl, 0), core(nc, 0);
+    std::vector<uint64_t> target_ids;
+    if (!taut && refuted_at != UINT64_MAX) {
+        auto it = T.refuted.find(refuted_at);
+        if (it == T.refuted.end()) return trim_fail(s, "no worker traced the refutation");
         // under the negated target a clause whose literal the target assumes is satisfied, and one that gives a literal of
         // the target ends the derivation
         std::unordered_map<int32_t, int> tl;
-        for (uint32_t k = doff[nl]; k < doff[nl + 1]; k++) tl[dl[k]] = 1;
+        for (uint32_t k = C.doff[nl]; k < C.doff[nl + 1]; k++) tl[C.dl[k]] = 1;
         for (size_t k = 0; k < it->second.ids.size(); k++) {
             const int32_t x = it->second.implied[k];
             if (x >= 0 && tl.count(x ^ 1)) continue;
             target_ids.push_back(it->second.ids[k]);
             if (x >= 0 && tl.count(x)) break;
         }
-    } else {
-        if (!T.have[nl]) return fail("the target's check was not traced");
+    } else if (!taut) {
+        if (!T.have[nl]) return trim_fail(s, "the target's check was not traced");
         target_ids = T.deps[nl];
     }
-    const uint64_t upper = std::min<uint64_t>(nl, info.refuted_at);
+    const uint64_t upper = std::min(nl, refuted_at);
     auto use = [&](const std::vector<uint64_t>& ids, uint64_t below) {
         for (uint64_t id : ids) {
             if (id < nc) core[id] = 1;
@@ -2990,36 +3087,33 @@ int trim_reach(mi355sat& s, TrimRun& T, const ProofLemmas& pf, const std::vector
         }
         return true;
     };
-    if (!use(target_ids, upper)) return fail("the target rests on a lemma behind the refutation");
+    if (!use(target_ids, upper)) return trim_fail(s, "the target rests on a lemma behind the refutation");
     for (uint64_t j = upper; j-- > 0;) {
         if (!needed[j]) continue;
-        if (!T.have[j]) return fail("a needed lemma's check was not traced");
-        if (!use(T.deps[j], j)) return fail("a lemma rests on a later one");
+        if (!T.have[j]) return trim_fail(s, "a needed lemma's check was not traced");
+        if (!use(T.deps[j], j)) return trim_fail(s, "a lemma rests on a later one");
     }
-    R.n_clauses = nc;
-    R.n_lemmas = nl;
-    R.hints = (T.flags & MI355SAT_TRIM_HINTS) != 0;
-    for (uint64_t c = 0; c < nc; c++) if (core[c]) R.core.push_back(c);
-    auto lrat = [&](const std::vector<uint64_t>& ids) {
-        std::vector<uint64_t> h;
-        for (uint64_t id : ids) h.push_back(id + 1);
-        return h;
-    };
-    for (uint64_t j = 0; j <= nl; j++) {
-        if (j < nl && !needed[j]) continue;
-        if (j < nl) R.lemmas.push_back(j);
-        R.lits.insert(R.lits.end(), pf.lits.begin() + pf.offs[j], pf.lits.begin() + pf.offs[j + 1]);
-        R.offs.push_back(R.lits.size());
-        if (R.hints) R.hint.push_back(lrat(j < nl ? T.deps[j] : target_ids));
-    }
-    R.valid = true;
-    T.out->core_clauses = R.core.size();
-    T.out->lemmas_needed = R.lemmas.size();
+    std::vector<uint64_t> core_ids, lemma_ids;
+    for (uint64_t c = 0; c < nc; c++) if (core[c]) core_ids.push_back(c);
+    for (uint64_t j = 0; j < nl; j++) if (needed[j]) lemma_ids.push_back(j);
+    trim_publish(s, T, C.pf, core_ids, lemma_ids, target_ids, taut);
     return 0;
 }
 
-int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info,
-                     TrimRun* T = nullptr) {
+// The trim after a verdict "valid": the reach - or, where the caller's clauses fell before any launch (an empty clause,
+// contradictory units), that clause or that pair as the core and as the hints of the one line, the target's.
+int trim_finish(mi355sat& s, TrimRun& T, const ProofCheck& C) {
+    if (!C.P.unsat) return trim_reach(s, T, C);
+    const std::vector<uint64_t> unsat_core = trim_maps(s, T);
+    if (unsat_core.empty()) return trim_fail(s, "the refuting clauses were not found");
+    trim_publish(s, T, C.pf, unsat_core, {}, unsat_core, false);
+    return 0;
+}
+
+// ---- the stages of a check (check_proof_impl runs them in this order) ----------------------------------------------------------
+// 1. The target: validated, appended as the last item; the sizes a worker's clause store can index.
+int proof_target(mi355sat& s, ProofCheck& C, const int32_t* target, uint64_t n_target) {
+    ProofLemmas& pf = C.pf;
     for (uint64_t i = 0; i < n_target; i++) {
         if (target[i] == 0 || target[i] == INT32_MIN) { s.err = "proof target: literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
         if (var_of(target[i]) > s.max_var) { s.err = "proof target: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
@@ -3030,151 +3124,125 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
     }
     pf.lits.insert(pf.lits.end(), target, target + n_target);
     pf.offs.push_back(pf.lits.size());
-    const uint32_t n_items = (uint32_t)pf.n_lemmas + 1;       // the target is lemma number n_lemmas
-    info.n_lemmas = pf.n_lemmas;
-    info.n_deletions_ignored = pf.n_deletions;
-    info.first_failed = info.refuted_at = UINT64_MAX;
+    C.n_items = (uint32_t)pf.n_lemmas + 1;       // the target is lemma number n_lemmas
+    C.info.n_lemmas = pf.n_lemmas;
+    C.info.n_deletions_ignored = pf.n_deletions;
+    C.info.first_failed = C.info.refuted_at = UINT64_MAX;
+    return 0;
+}
+
+// 2. The answers that need no launch (an interrupt is consumed before the slabs are given up).  true: info.valid has one.
+bool proof_without_launch(mi355sat& s, ProofCheck& C) {
     if (s.interrupted.load()) {      // as a solve: an interrupt that came before the call stops it at once
         consume_interrupt(s);
-        info.valid = -1;
-        return MI355SAT_INTERRUPTED;
+        C.info.valid = -1;           // (check_proof_impl returns MI355SAT_INTERRUPTED for it)
+        return true;
     }
     go_cold(s, MI355SAT_COLD_OTHER_SEARCH);      // (the slabs become this check's)
     s.ph.on_device = false;
-    Prepared P;
-    prepare(s, /*simplify=*/false, P, /*identity_order=*/true);
-    std::vector<uint64_t> unsat_core;
-    if (T) trim_maps(s, *T, unsat_core);
-    if (P.unsat) {               // an empty clause or contradictory units among the caller's clauses
-        info.refuted_at = 0;
-        info.valid = 1;
-        if (T) {                 // the core is that clause or that pair: one LRAT line, the target's
-            if (unsat_core.empty()) { s.err = "proof trim: the refuting clauses were not found"; return MI355SAT_ERR_HIP; }
-            mi355sat::Trim& R = s.trim;
-            R.n_clauses = T->n_clauses;
-            R.n_lemmas = pf.n_lemmas;
-            R.hints = (T->flags & MI355SAT_TRIM_HINTS) != 0;
-            R.core = unsat_core;
-            std::sort(R.core.begin(), R.core.end());
-            R.lits.assign(target, target + n_target);
-            R.offs.push_back(R.lits.size());
-            if (R.hints) {
-                R.hint.emplace_back();
-                for (uint64_t c : unsat_core) R.hint.back().push_back(c + 1);
-            }
-            R.valid = true;
-            T->out->core_clauses = R.core.size();
-        }
-        return 0;
-    }
-    if (P.n_vars == 0) {         // no variable, no clause: only empty lemmas are possible, and none is RUP
-        info.first_failed = 0;
-        info.valid = 0;
-        return 0;
-    }
-    // the proof as the device reads it: device literals, each variable at most once per lemma; x and ~x: skipped
-    std::vector<int32_t> dl;
-    std::vector<uint32_t> doff{0};
-    std::vector<uint8_t> skip(n_items, 0);
-    dl.reserve(pf.lits.size() + 4);
-    uint64_t store_lits = 0;
-    // (the lemma's own literal order is kept - a solver writes the asserting literal first, and the first two free literals
-    // become the watches: sorted, the lists of the lowest variables would hold most of the proof)
+    prepare(s, /*simplify=*/false, C.P, /*identity_order=*/true);
+    if (C.P.unsat) {             // an empty clause or contradictory units among the caller's clauses
+        C.info.refuted_at = 0;
+        C.info.valid = 1;
+    } else if (C.P.n_vars == 0) {    // no variable, no clause: only empty lemmas are possible, and none is RUP
+        C.info.first_failed = 0;
+        C.info.valid = 0;
+    } else return false;
+    return true;
+}
+
+// 3. The proof as the device reads it.  An item's own literal order is kept - a solver writes the asserting literal first,
+// and the first two free literals become the watches: sorted, the lists of the lowest variables would hold most of the proof.
+void proof_device_form(ProofCheck& C) {
+    const ProofLemmas& pf = C.pf;
+    C.skip.assign(C.n_items, 0);
+    C.dl.reserve(pf.lits.size() + 4);
     std::vector<int32_t> tmp;
-    std::vector<uint32_t> stamp(P.n_vars, 0);       // per variable: 2 * (j + 1) | sign of its literal in lemma j
-    for (uint32_t j = 0; j < n_items; j++) {
+    std::vector<uint32_t> stamp(C.P.n_vars, 0);     // per variable: 2 * (j + 1) | sign of its literal in lemma j
+    for (uint32_t j = 0; j < C.n_items; j++) {
         tmp.clear();
         for (uint64_t k = pf.offs[j]; k < pf.offs[j + 1]; k++) {
-            const int32_t l = to_device(P.perm, pf.lits[k]);
+            const int32_t l = to_device(C.P.perm, pf.lits[k]);
             uint32_t& st = stamp[l >> 1];
             if ((st >> 1) != j + 1) { st = 2 * (j + 1) | (uint32_t)(l & 1); tmp.push_back(l); }
-            else if ((st & 1u) != (uint32_t)(l & 1)) skip[j] = 1;
+            else if ((st & 1u) != (uint32_t)(l & 1)) C.skip[j] = 1;
         }
-        if (skip[j]) tmp.clear();
-        dl.insert(dl.end(), tmp.begin(), tmp.end());
-        doff.push_back((uint32_t)dl.size());
-        if (j + 1 < n_items) store_lits += (tmp.size() + 3) & ~(size_t)3;
+        if (C.skip[j]) tmp.clear();
+        C.dl.insert(C.dl.end(), tmp.begin(), tmp.end());
+        C.doff.push_back((uint32_t)C.dl.size());
+        if (j + 1 < C.n_items) C.store_lits += (tmp.size() + 3) & ~(size_t)3;
     }
-    for (int k = 0; k < 4; k++) dl.push_back(0);
-    // a worker's learnt store: every lemma, each 16-byte aligned (add_learnt wants 8 words of headroom)
-    const uint32_t learnt_cap = (uint32_t)pf.n_lemmas + 1;
-    const uint32_t learnt_lit_cap = (uint32_t)(store_lits + 16);
-    uint32_t S = segments ? segments : fleet_size(s);
-    S = std::min(S, n_items);
-    upload_formula(s, P, 0, /*script_cap=*/8, S, 0, learnt_cap, learnt_lit_cap, MI355SAT_ERR_OOM);
+    for (int k = 0; k < 4; k++) C.dl.push_back(0);
+}
+
+// 4. The formula to the device with a learnt store that holds every lemma (each 16-byte aligned; add_learnt wants 8 words
+// of headroom), one worker per segment with its script - cursor, a, b, pad, checked (64 bit), attached (64 bit) - and
+// the proof behind it.
+void proof_upload(mi355sat& s, ProofCheck& C, uint32_t segments) {
+    const uint32_t learnt_cap = (uint32_t)C.pf.n_lemmas + 1;
+    const uint32_t learnt_lit_cap = (uint32_t)(C.store_lits + 16);
+    uint32_t S = std::min(segments ? segments : fleet_size(s), C.n_items);
+    upload_formula(s, C.P, 0, /*script_cap=*/8, S, 0, learnt_cap, learnt_lit_cap, MI355SAT_ERR_OOM);
     S = std::min(S, s.n_workers);                // (what device memory holds)
     s.n_workers = s.n_alloc = S;
-    info.segments = info.workers = S;
-    std::vector<int32_t> script;                 // per worker: cursor, a, b, pad, checked (64 bit), attached (64 bit)
+    C.S = C.info.segments = C.info.workers = S;
+    std::vector<int32_t> script;
     std::vector<uint64_t> soff{0};
     for (uint32_t w = 0; w < S; w++) {
-        const int32_t a = (int32_t)((uint64_t)n_items * w / S), b = (int32_t)((uint64_t)n_items * (w + 1) / S);
+        const int32_t a = (int32_t)((uint64_t)C.n_items * w / S), b = (int32_t)((uint64_t)C.n_items * (w + 1) / S);
         script.insert(script.end(), {0, a, b, 0, 0, 0, 0, 0});
         soff.push_back(script.size());
     }
     reset_workers(s);
     customize(s, nullptr, nullptr, &script, &soff, S);
-    DevBuf<int32_t> d_lits;
-    DevBuf<uint32_t> d_offs;
-    DevBuf<uint8_t> d_skip;
-    DevBuf<unsigned long long> d_mins;
-    d_lits.upload(dl, s.stream);
-    d_offs.upload(doff, s.stream);
-    d_skip.upload(skip, s.stream);
-    d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
-    MsTrace mt{};
-    if (T) {
-        // a worker ends its launch when its region has less room than two items of the largest size: never size one below that
-        const uint64_t floor_words = 2 * MS_TR_ITEM_WORDS(P.n_vars);
-        const uint64_t rule = std::min<uint64_t>(1u << 18, (1u << 26) / S);
-        T->words = (uint32_t)std::max<uint64_t>(floor_words, s.trim_log_words ? s.trim_log_words : rule);
-        T->out->log_words_per_worker = T->words;
-        T->d_log.alloc((size_t)S * T->words);
-        T->d_used.upload(std::vector<uint32_t>(S, 0u), s.stream);
-        T->deps.assign(n_items, {});
-        T->have.assign(n_items, 0);
-        mt = MsTrace{T->d_log.p, T->d_used.p, T->words, 0};
-    }
-    HIPCHK(hipStreamSynchronize(s.stream));
-    const uint32_t chunk = s.proof_chunk;
+    C.d_lits.upload(C.dl, s.stream);
+    C.d_offs.upload(C.doff, s.stream);
+    C.d_skip.upload(C.skip, s.stream);
+    C.d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
+}
+
+// 5. Launches until no worker is running, the interrupt flag polled between them; a traced check's log drained after each.
+int proof_launches(mi355sat& s, ProofCheck& C, TrimRun* T) {
     const double k0 = s.stats.kernel_seconds;
     std::vector<MsState> sts;
-    bool interrupted = false;
     for (;;) {
-        if (s.interrupted.load()) { interrupted = true; break; }
-        launch_rup(s, S, chunk, d_lits.p, d_offs.p, d_skip.p, n_items, d_mins.p, T ? &mt : nullptr);
-        info.launches++;
+        if (s.interrupted.load()) { C.interrupted = true; break; }
+        launch_rup(s, C, T ? T->mt : MsTrace{});
+        C.info.launches++;
         gather_states(s, sts);
-        if (T) if (int rc = trim_drain(s, *T, S, n_items)) return rc;
+        if (T) if (int rc = trim_drain(s, *T, C.S, C.n_items)) return rc;
         bool running = false;
-        for (uint32_t w = 0; w < S; w++) {
-            if (sts[w].status < 0) {
-                s.err = std::string("proof check: ") + status_text(sts[w].status);
-                return sts[w].status == MS_ST_ERR_INTERNAL ? MI355SAT_ERR_HIP : MI355SAT_ERR_OOM;
-            }
+        for (uint32_t w = 0; w < C.S; w++) {
+            if (sts[w].status < 0) return status_error(s, sts[w].status, MI355SAT_ERR_HIP, "proof check: ");
             running = running || sts[w].status == MS_ST_RUNNING;
         }
         if (!running) break;
     }
-    info.kernel_seconds = s.stats.kernel_seconds - k0;
-    for (const MsState& st : sts) info.propagations += st.propagations;
+    C.info.kernel_seconds = s.stats.kernel_seconds - k0;
+    for (const MsState& st : sts) C.info.propagations += st.propagations;
+    return 0;
+}
+
+// 6. The workers' counters, and unless an interrupt ended the check (valid = -1) the verdict.
+int proof_verdict(mi355sat& s, ProofCheck& C) {
+    mi355sat_proof_info& info = C.info;
     if (info.launches) {
-        std::vector<int32_t> sc((size_t)S * 8);
-        HIPCHK(hipMemcpy2D(sc.data(), 32, s.d_slabs.p + s.L.script, s.L.slab_bytes, 32, S, hipMemcpyDeviceToHost));
-        for (uint32_t w = 0; w < S; w++) {
+        std::vector<int32_t> sc((size_t)C.S * 8);
+        HIPCHK(hipMemcpy2D(sc.data(), 32, s.d_slabs.p + s.L.script, s.L.slab_bytes, 32, C.S, hipMemcpyDeviceToHost));
+        for (uint32_t w = 0; w < C.S; w++) {
             uint64_t c[2];
             memcpy(c, &sc[(size_t)w * 8 + 4], sizeof c);
             info.lemmas_checked += c[0];
             info.lemmas_attached += c[1];
         }
     }
-    if (interrupted) {
+    if (C.interrupted) {
         consume_interrupt(s);
         info.valid = -1;
-        return MI355SAT_INTERRUPTED;
+        return 0;
     }
     unsigned long long mins[2];
-    HIPCHK(hipMemcpy(mins, d_mins.p, sizeof mins, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mins, C.d_mins.p, sizeof mins, hipMemcpyDeviceToHost));
     info.first_failed = ~mins[0];
     info.refuted_at = ~mins[1];
     // (a lemma behind the point of refutation is RUP whatever a worker that had not seen the refuting lemmas yet made of it:
@@ -3184,29 +3252,52 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
         return MI355SAT_ERR_HIP;
     }
     info.valid = info.first_failed == UINT64_MAX ? 1 : 0;
-    if (T && info.valid == 1) return trim_reach(s, *T, pf, skip, dl, doff, info);
     return 0;
 }
 
-// trim (may be null): the traced check of mi355sat_trim_proof, whose result stays on the handle.
-int check_proof_entry(mi355sat* s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info* out,
-                      mi355sat_trim_info* trim = nullptr, uint32_t flags = 0) {
+// T (may be null): mi355sat_trim_proof's traced check, which attaches before the launch (trim_begin), after each launch
+// (trim_drain, in proof_launches) and after a verdict "valid" (trim_finish).
+int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info,
+                     TrimRun* T) {
+    ProofCheck C{pf, info};
+    if (int rc = proof_target(s, C, target, n_target)) return rc;
+    if (!proof_without_launch(s, C)) {
+        proof_device_form(C);
+        proof_upload(s, C, segments);
+        if (T) trim_begin(s, *T, C);
+        HIPCHK(hipStreamSynchronize(s.stream));
+        if (int rc = proof_launches(s, C, T)) return rc;
+        if (int rc = proof_verdict(s, C)) return rc;
+    }
+    if (info.valid < 0) return MI355SAT_INTERRUPTED;     // before the call or between two launches
+    return T && info.valid == 1 ? trim_finish(s, *T, C) : 0;
+}
+
+// The one body of mi355sat_check_proof, _trim_proof and their _file variants (name: the entry's in its messages).  The words
+// come from memory or, with a path, from a DRUP text file; trim (may be null): the traced check, whose result stays on the
+// handle, instead of the plain one that fills `out`.
+int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_words, const char* path, const int32_t* target,
+                uint64_t n_target, uint32_t segments, mi355sat_proof_info* out, mi355sat_trim_info* trim = nullptr, uint32_t flags = 0) {
+    if (s->sweep) { s->err = std::string(name) + "() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = std::string(name) + "() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    ProofLemmas pf;
+    if (int rc = guarded(s, GUARD_HOST, [&] {
+            std::vector<int32_t> text;
+            if (!path) return parse_proof_words(*s, words, n_words, pf);
+            if (int e = read_proof_file(*s, path, text)) return e;
+            return parse_proof_words(*s, text.data(), text.size(), pf);
+        })) return rc;
+    // (every refusal above leaves an earlier trim_proof's result on the handle; a bad target is refused below, after the drop)
     mi355sat_proof_info info{};
     const double t0 = now_s();
     s->trim.drop();
-    int rc;
-    if (trim) {
-        TrimRun T;
-        *trim = mi355sat_trim_info{};
-        T.flags = flags;
-        T.out = trim;
-        rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info, &T); });
-        if (rc < 0 || info.valid != 1) s->trim.drop();
-    } else rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info); });
+    TrimRun T{flags, trim};          // (used by a trim only)
+    if (trim) *trim = mi355sat_trim_info{};
+    const int rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info, trim ? &T : nullptr); });
+    if (rc < 0 || info.valid != 1) s->trim.drop();
     info.seconds = now_s() - t0;
     if (rc < 0) go_cold(*s, MI355SAT_COLD_FIRST);
-    if (trim) trim->check = info;
-    else *out = info;
+    *(trim ? &trim->check : out) = info;
     return rc;
 }
 
@@ -3362,6 +3453,11 @@ int mi355sat_failed(mi355sat* s, int32_t lit) {
     return std::find(s->core.lits.begin(), s->core.lits.end(), lit) != s->core.lits.end() ? 1 : 0;
 }
 
+// A model (one byte per caller variable) into a caller's buffer of n_vars entries: 0 behind the model's end.
+static void copy_model(const std::vector<int8_t>& m, int8_t* out, uint64_t n_vars) {
+    for (uint64_t v = 0; v < n_vars; v++) out[v] = v < m.size() ? m[v] : 0;
+}
+
 static int copy_core(mi355sat* s, const Core& core, int32_t* out, uint64_t cap, uint64_t* n) {
     if (n) *n = core.lits.size();
     if (!out) return 0;
@@ -3471,25 +3567,13 @@ int mi355sat_set_proof_path(mi355sat* s, const char* path) {
 int mi355sat_check_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
                          uint32_t segments, mi355sat_proof_info* out) {
     if (!s || !out || (n_words && !proof) || (n_target && !target)) return MI355SAT_ERR_ARG;
-    if (s->sweep) { s->err = "check_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
-    if (!s->pending.empty()) { s->err = "check_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
-    ProofLemmas pf;
-    if (int rc = guarded(s, GUARD_HOST, [&] { return parse_proof_words(*s, proof, n_words, pf); })) return rc;
-    return check_proof_entry(s, pf, target, n_target, segments, out);
+    return proof_entry(s, "check_proof", proof, n_words, nullptr, target, n_target, segments, out);
 }
 
 int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
                               mi355sat_proof_info* out) {
     if (!s || !out || !path || (n_target && !target)) return MI355SAT_ERR_ARG;
-    if (s->sweep) { s->err = "check_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
-    if (!s->pending.empty()) { s->err = "check_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
-    ProofLemmas pf;
-    if (int rc = guarded(s, GUARD_HOST, [&] {
-            std::vector<int32_t> words;
-            if (int e = read_proof_file(*s, path, words)) return e;
-            return parse_proof_words(*s, words.data(), words.size(), pf);
-        })) return rc;
-    return check_proof_entry(s, pf, target, n_target, segments, out);
+    return proof_entry(s, "check_proof", nullptr, 0, path, target, n_target, segments, out);
 }
 
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch) {
@@ -3501,25 +3585,13 @@ int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch
 int mi355sat_trim_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
                         uint32_t segments, uint32_t flags, mi355sat_trim_info* out) {
     if (!s || !out || (n_words && !proof) || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
-    if (s->sweep) { s->err = "trim_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
-    if (!s->pending.empty()) { s->err = "trim_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
-    ProofLemmas pf;
-    if (int rc = guarded(s, GUARD_HOST, [&] { return parse_proof_words(*s, proof, n_words, pf); })) return rc;
-    return check_proof_entry(s, pf, target, n_target, segments, nullptr, out, flags);
+    return proof_entry(s, "trim_proof", proof, n_words, nullptr, target, n_target, segments, nullptr, out, flags);
 }
 
 int mi355sat_trim_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
                              uint32_t flags, mi355sat_trim_info* out) {
     if (!s || !out || !path || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
-    if (s->sweep) { s->err = "trim_proof() called during a sweep"; return MI355SAT_ERR_STATE; }
-    if (!s->pending.empty()) { s->err = "trim_proof() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
-    ProofLemmas pf;
-    if (int rc = guarded(s, GUARD_HOST, [&] {
-            std::vector<int32_t> words;
-            if (int e = read_proof_file(*s, path, words)) return e;
-            return parse_proof_words(*s, words.data(), words.size(), pf);
-        })) return rc;
-    return check_proof_entry(s, pf, target, n_target, segments, nullptr, out, flags);
+    return proof_entry(s, "trim_proof", nullptr, 0, path, target, n_target, segments, nullptr, out, flags);
 }
 
 static int trim_result(mi355sat* s) {
@@ -3718,7 +3790,7 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
         }
         gather_states(*s, sts);
         for (uint64_t i = 0; i < n_instances; i++) {
-            if (sts[i].status < 0) { s->err = status_text(sts[i].status); return MI355SAT_ERR_OOM; }
+            if (sts[i].status < 0) return status_error(*s, sts[i].status, MI355SAT_ERR_OOM);
             if (out_conflict) out_conflict[i] = sts[i].status == MS_ST_UNSAT ? 1 : 0;
             if (out_trail_len) out_trail_len[i] = sts[i].trail_n;
         }
@@ -3835,7 +3907,7 @@ int mi355sat_sweep_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_
         }
         std::vector<int8_t> m;
         fetch_model(*s, (uint32_t)sw.winner[instance], m, s->max_var);
-        for (uint64_t v = 0; v < n_vars; v++) out[v] = v < m.size() ? m[v] : 0;
+        copy_model(m, out, n_vars);
         return 0;
     });
 }
@@ -3868,7 +3940,7 @@ int32_t mi355sat_val(mi355sat* s, int32_t lit) {
 int mi355sat_model(mi355sat* s, int8_t* out, uint64_t n_vars) {
     if (!s || !out) return MI355SAT_ERR_ARG;
     if (s->model.empty() && s->max_var) { s->err = "no model (last result was not SAT)"; return MI355SAT_ERR_STATE; }
-    for (uint64_t v = 0; v < n_vars; v++) out[v] = v < s->model.size() ? s->model[v] : 0;
+    copy_model(s->model, out, n_vars);
     return 0;
 }
 
@@ -3878,8 +3950,7 @@ int mi355sat_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_t n_va
         s->err = "no model for that instance";
         return MI355SAT_ERR_STATE;
     }
-    const auto& m = s->batch_models[instance];
-    for (uint64_t v = 0; v < n_vars; v++) out[v] = v < m.size() ? m[v] : 0;
+    copy_model(s->batch_models[instance], out, n_vars);
     return 0;
 }
 
@@ -3894,8 +3965,7 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
         const uint64_t live = std::min<uint64_t>(n, s->share_slots);
         std::vector<int32_t> ring((size_t)live * MS_SHARE_REC);
         if (live) HIPCHK(hipMemcpy(ring.data(), s->d_share_pool.p, ring.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> inv(s->perm.size());
-        for (uint32_t e = 0; e < s->perm.size(); e++) inv[s->perm[e]] = e;
+        const std::vector<uint32_t> inv = inverse_order(s->perm);
         uint64_t w = 0;
         for (uint64_t r = 0; r < live; r++) {
             const int32_t* rec = ring.data() + r * MS_SHARE_REC;
@@ -3904,7 +3974,7 @@ int mi355sat_debug_share_ring(mi355sat* s, int32_t* out, uint64_t cap_words, uin
             if (out && w + (uint64_t)sz + 1 <= cap_words) {
                 for (int j = 1; j <= sz; j++) {
                     if (rec[j] < 0 || (uint32_t)(rec[j] >> 1) >= inv.size()) { s->err = "literal out of range in the exchange ring"; return MI355SAT_ERR_STATE; }
-                    out[w + j - 1] = (rec[j] & 1) ? -((int32_t)inv[rec[j] >> 1] + 1) : ((int32_t)inv[rec[j] >> 1] + 1);
+                    out[w + j - 1] = to_dimacs(inv, rec[j]);
                 }
                 out[w + sz] = 0;
             }
@@ -3979,8 +4049,7 @@ int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_
                              cnt * MS_SHARE_REC * sizeof(int32_t), hipMemcpyDeviceToHost));
             r += cnt;
         }
-        std::vector<uint32_t> inv(s->perm.size());
-        for (uint32_t e = 0; e < s->perm.size(); e++) inv[s->perm[e]] = e;
+        const std::vector<uint32_t> inv = inverse_order(s->perm);
         uint64_t w = 0, consumed = from;
         for (uint64_t r = from; r < n; r++) {
             const int32_t* rec = recs.data() + (r - from) * MS_SHARE_REC;
@@ -3992,7 +4061,7 @@ int mi355sat_share_export(mi355sat* s, int32_t* out, uint64_t cap_words, uint64_
                 out[w] = (int32_t)std::max<uint32_t>(1u, (hdr >> 6) & 255u);
                 for (int j = 1; j <= sz; j++) {
                     if (rec[j] < 0 || (uint32_t)(rec[j] >> 1) >= inv.size()) { s->err = "literal out of range in the exchange ring"; return MI355SAT_ERR_STATE; }
-                    out[w + j] = (rec[j] & 1) ? -((int32_t)inv[rec[j] >> 1] + 1) : ((int32_t)inv[rec[j] >> 1] + 1);
+                    out[w + j] = to_dimacs(inv, rec[j]);
                 }
                 out[w + sz + 1] = 0;
             }
