@@ -125,7 +125,8 @@ typedef struct mi355sat_opts {
                                   k = 11 / rect 32 k = 14 10.5 / 15.9 s without, 12.9 / 17.6 s with, profiles/r03_m_knob_sweep2.log).  No effect in
                                   launches of more than 2048 workers: the full-fleet build leaves the code out */
     int32_t rebalance;         /* batched solves: 0 = default (on): workers of decided / withdrawn instances move to the open
-                                  ones; -1 = they park */
+                                  ones; -1 = they park, and a worker parked for a withdrawn instance resumes that instance
+                                  (no other) when mi355sat_sweep_reopen takes it up again */
     int32_t deterministic;     /* 0 = default: time-bounded slices (all workers stop together; what a worker does in a slice, and
                                   with it the whole trajectory, depends on timing); 1 = a reproducible mode for benchmarks and
                                   A/B comparisons: slices are bounded by conflicts per worker (slice_conflicts, default 200), no
@@ -330,8 +331,12 @@ int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* as
 int mi355sat_sweep_begin(mi355sat* s, const int32_t* assumps, const uint64_t* assump_offsets, uint64_t n_instances);
 int mi355sat_sweep_step(mi355sat* s, int32_t* results /* may be NULL */, uint64_t* n_decided /* may be NULL */);
 /* Withdraw instances whose answer the caller no longer needs (in the decreasing-k sweep: every k above a
- * SAT one and every k below an UNSAT one is implied).  Their result stays 0, they count as decided, and
- * their workers move to the instances still open - as do the workers of every instance that gets its verdict. */
+ * SAT one and every k below an UNSAT one is implied).  Their result stays 0 for as long as they are withdrawn, they
+ * count as decided, and their workers move to the instances still open - as do the workers of every instance that gets
+ * its verdict (opts.rebalance = -1: they park).  Withdrawing a decided or withdrawn instance, or none, changes nothing.
+ * opts.cube_split = 1: the cubes of a withdrawn instance stay with their workers, which go on searching and splitting
+ * them; the closed-cube accounting is kept - a cube that closes (or finds a model) while its instance is withdrawn stays
+ * with its worker, and is counted, the verdict with it, at the first mi355sat_sweep_step after mi355sat_sweep_reopen. */
 int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n);
 /* Priorities: open instance i gets about weights[i] / sum(weights of open instances) of the workers from the next
  * step on (workers move between open instances if need be; they keep their learnt clauses).  The decreasing-k loop
@@ -339,8 +344,12 @@ int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n);
  * and the lowest open one (a refutation there raises the floor).  n must be the number of instances. */
 int mi355sat_sweep_set_weights(mi355sat* s, const double* weights, uint64_t n);
 /* Take withdrawn, still undecided instances up again: idle workers (parked, or of decided / withdrawn instances)
- * move to them.  The sharded sweep (one process per GPU) begins every rank with all bounds, withdraws
- * the other ranks' shards, and reopens the bounds still open anywhere once its own shard is decided. */
+ * move to them.  With opts.rebalance = -1 nothing moves, but a worker that parked when its OWN instance was withdrawn
+ * goes back to that instance's list, from level 0.  A reopened instance is decided again in every mode; its verdict is
+ * reported by the steps that follow (at once, as UNSAT, if a worker has refuted the formula itself meanwhile).
+ * Reopening an instance that is not withdrawn, or none, changes nothing.  The sharded sweep (one process per GPU,
+ * SURVEY 8e) begins every rank with all bounds, withdraws the other ranks' shards, and reopens the bounds still open
+ * anywhere once its own shard is decided. */
 int mi355sat_sweep_reopen(mi355sat* s, const uint64_t* instances, uint64_t n);
 /* Model of an instance that already reported SAT, while the sweep is still running (the loop needs the
  * layout's platform count to know which bounds it answers). */

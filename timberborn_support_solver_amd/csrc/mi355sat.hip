@@ -1868,6 +1868,7 @@ struct Sweep {
     uint64_t n_moved = 0;
     float ramp_ms = 0;                           // kernel time of this sweep so far
     uint32_t decided = 0;
+    bool formula_unsat = false;                  // a worker refuted the formula itself: whatever is reopened is UNSAT too
     bool stop_at_first = false;
     bool active = false;
     std::vector<MsState> sts;
@@ -1911,7 +1912,7 @@ struct Sweep {
         n_instances = n;
         stop_at_first = first_only;
         decided = 0;
-        active = split = false;
+        active = split = formula_unsat = false;
         n_moved = 0;
         ramp_ms = 0;
         counters0.clear();
@@ -1958,6 +1959,22 @@ struct WorkerUpdates {
     // more follows on the stream - no `data`, no wait.
     void send(mi355sat& s, Sweep& sw, const int32_t* resident = nullptr) {
         if (upd.empty()) return;
+        // One record per worker: the records of a launch are applied by workgroups in no particular order, so of two for
+        // one worker (parked because its instance was decided and handed a stolen cube in the same pass of schedule_cubes;
+        // woken and moved on in one pass of rebalance_workers) either could come last.  The later one holds, a restart
+        // request of either stays.
+        {
+            std::vector<int32_t> last;
+            std::vector<size_t> at_of;     // worker -> its record in `last`, + 1
+            for (size_t r = upd.size() / 5; r-- > 0;) {
+                const size_t w = (size_t)upd[5 * r];
+                if (w >= at_of.size()) at_of.resize(w + 1, 0);
+                if (at_of[w]) { last[at_of[w] - 1 + 2] |= upd[5 * r + 2]; continue; }
+                at_of[w] = last.size() + 1;
+                last.insert(last.end(), upd.begin() + 5 * r, upd.begin() + 5 * r + 5);
+            }
+            upd.swap(last);
+        }
         const uint32_t n = (uint32_t)(upd.size() / 5);
         sw.d_upd.upload(upd, s.stream);
         if (!resident) sw.d_data.upload_nonempty(data, s.stream);
@@ -2101,7 +2118,8 @@ void schedule_cubes(mi355sat& s, Sweep& sw) {
             sw.w_busy[w] = 0;
             if (sw.sts[w].status == MS_ST_RUNNING) { sw.w_cube[w].clear(); u.add(w, MS_ST_PARKED, 0, sw.w_cube[w]); sw.sts[w].status = MS_ST_PARKED; }
         }
-        if (!sw.w_busy[w]) idle.push_back(w);
+        const bool keeps_model = sw.results[sw.w_inst[w]] == MI355SAT_SAT && sw.winner[sw.w_inst[w]] == (int32_t)w;
+        if (!sw.w_busy[w]) { if (!keeps_model) idle.push_back(w); }   // (mi355sat_sweep_model_of / _sweep_end read the winner's slab)
         else if (sw.sts[w].status == MS_ST_RUNNING && sw.sts[w].n_split > 0) victims.push_back(w);
     }
     // hardest cubes first: most conflicts spent on the current cube
@@ -2146,16 +2164,28 @@ inline bool inst_open(const Sweep& sw, uint32_t inst) { return sw.results[inst] 
 void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
     const uint32_t n_instances = sw.n_instances;
     std::vector<uint32_t> cnt(n_instances, 0), movable;
+    WorkerUpdates u;
     for (uint32_t w = 0; w < s.n_alloc; w++) {   // (a worker without a slab yet is picked up after grow_workers)
         const uint32_t inst = (uint32_t)sw.w_inst[w];
         const int st = sw.sts[w].status;
-        if (!all && inst_open(sw, inst)) { if (st == MS_ST_RUNNING) cnt[inst]++; continue; }
+        if (!all && inst_open(sw, inst)) {
+            // parked when its instance was withdrawn (opts.rebalance = -1, or nothing was open), and the instance is open
+            // again: back to its own list, from level 0.  Not a migration - it holds with rebalancing off too.  (A worker
+            // that FINISHED its withdrawn instance - MS_ST_SAT, MS_ST_REFUTED - stays as it is: sweep_step takes its verdict.)
+            if (st == MS_ST_PARKED) {
+                sw.w_busy[w] = 1;
+                sw.w_cube[w].assign(sw.base_assump.begin() + sw.base_off[inst], sw.base_assump.begin() + sw.base_off[inst + 1]);
+                u.add(w, MS_ST_RUNNING, 1, sw.w_cube[w]);
+                sw.sts[w].status = MS_ST_RUNNING;
+            }
+            if (sw.sts[w].status == MS_ST_RUNNING) cnt[inst]++;
+            continue;
+        }
         if (!all && sw.winner[inst] == (int32_t)w && sw.results[inst] == MI355SAT_SAT) continue;   // keeps the model
         if (st == MS_ST_RUNNING || st == MS_ST_SAT || st == MS_ST_REFUTED || st == MS_ST_PARKED) movable.push_back(w);
     }
     std::vector<uint32_t> open;
     for (uint32_t i = 0; i < n_instances; i++) if (inst_open(sw, i)) open.push_back(i);
-    WorkerUpdates u;
     auto park = [&](uint32_t w) {
         if (sw.sts[w].status != MS_ST_RUNNING) return;
         u.add(w, MS_ST_PARKED, 0, {});
@@ -2422,6 +2452,10 @@ int sweep_step(mi355sat& s, Sweep& sw) {
         if (st.status < 0) rc = status_error(s, st.status, MI355SAT_ERR_STATE);
         if (!sw.w_busy[w]) continue;
         const uint32_t inst = (uint32_t)sw.w_inst[w];
+        // A worker that finishes the cube of a WITHDRAWN instance keeps it (busy, its status as it is; a non-running worker
+        // is not touched by a slice): the cube is closed, and the verdict taken, at the first step after mi355sat_sweep_reopen.
+        if (st.status == MS_ST_UNSAT) sw.formula_unsat = true;
+        else if (sw.dropped[inst]) continue;
         if (st.status == MS_ST_REFUTED || st.status == MS_ST_UNSAT) {   // this worker's cube is closed
             sw.w_busy[w] = 0;
             sw.open[inst]--;
@@ -3886,6 +3920,7 @@ int mi355sat_sweep_reopen(mi355sat* s, const uint64_t* instances, uint64_t n) {
             const uint64_t i = instances[j];
             if (!sw.dropped[i] || sw.results[i] != MI355SAT_INTERRUPTED) continue;   // only what was withdrawn undecided
             sw.dropped[i] = 0;
+            if (sw.formula_unsat) { sw.results[i] = MI355SAT_UNSAT; continue; }   // the formula is refuted: no search (it stays counted)
             sw.decided--;
             any = true;
         }
