@@ -1854,9 +1854,32 @@ int status_error(mi355sat& s, int st, int internal, const char* prefix = "") {
     return st == MS_ST_ERR_INTERNAL ? internal : MI355SAT_ERR_OOM;
 }
 
+// The worker whose slab is the model of instance `inst` - it keeps that slab until the caller has read it - or -1.
+inline int32_t model_holder(const std::vector<int32_t>& results, const std::vector<int32_t>& winner, uint64_t inst) {
+    return results[inst] == MI355SAT_SAT ? winner[inst] : -1;
+}
+
+struct Sweep;
+
+// What the host tells workers between two slices, for ms_assign_kernel to apply: a new status, a restart request and a
+// new assumption list (the worker's cube) each.  Queued by Sweep::assign / park, which keep the host's side of it.
+struct WorkerUpdates {
+    std::vector<int32_t> upd, data;
+    // The record as ms_assign_kernel reads it, five words: worker, status, restart request, the length of its assumption
+    // list and where that starts in the launch's data buffer.
+    void add_at(uint32_t w, int32_t status, int32_t restart, size_t n, size_t at) {
+        upd.insert(upd.end(), {(int32_t)w, status, restart, (int32_t)n, (int32_t)at});
+    }
+    void add(uint32_t w, int32_t status, int32_t restart, const std::vector<int32_t>& cube) {   // the list travels in `data`
+        add_at(w, status, restart, cube.size(), data.size());
+        data.insert(data.end(), cube.begin(), cube.end());
+    }
+    void send(mi355sat& s, Sweep& sw, const int32_t* resident = nullptr);
+};
+
 // Shared driver for solve(), solve_batch() and the stepwise sweep API.
 // Worker w starts on instance w % n_instances; workers of decided (or withdrawn) instances move on
-// to the open ones (w_inst).
+// to the open ones (w_inst).  DESIGN.md §5 has the states of an instance and of a worker and who moves them.
 struct Sweep {
     uint32_t n_instances = 0;
     std::vector<int32_t> results, winner;
@@ -1867,7 +1890,7 @@ struct Sweep {
     std::vector<uint64_t> base_off;
     uint64_t n_moved = 0;
     float ramp_ms = 0;                           // kernel time of this sweep so far
-    uint32_t decided = 0;
+    uint32_t decided = 0;                        // instances that are not open
     bool formula_unsat = false;                  // a worker refuted the formula itself: whatever is reopened is UNSAT too
     bool stop_at_first = false;
     bool active = false;
@@ -1880,7 +1903,7 @@ struct Sweep {
     std::vector<std::vector<int32_t>> w_cube;   // internal literals
     std::vector<uint8_t> w_busy;
     std::vector<uint64_t> w_conf0;               // worker's conflict count when it got its cube
-    std::vector<uint32_t> open;                  // open cubes per instance
+    std::vector<uint32_t> open;                  // per instance: its busy workers (with splitting: its open cubes)
     uint64_t n_splits = 0, n_closed = 0;
     DevBuf<int32_t> d_upd, d_data;
     // failed-assumption cores (solve() and solve_batch() only; the public sweep API launches nothing for them): per
@@ -1898,12 +1921,34 @@ struct Sweep {
     std::vector<MsState> counters0;
     uint64_t conflicts0 = 0;
 
-    // Instance `inst` is posed (anew): open, no verdict, an empty core over its n_assumps entries of the caller's list.
+    // ---- an instance: open, withdrawn, SAT or UNSAT.  Only pose / decide / withdraw / reopen / reset write results, winner,
+    // dropped and decided.
+    bool is_open(uint32_t inst) const { return results[inst] == MI355SAT_INTERRUPTED && !dropped[inst]; }
+    // Posed (anew): open, no verdict, an empty core over its n_assumps entries of the caller's list.
     void pose(uint32_t inst, uint64_t n_assumps) {
+        if (!is_open(inst)) decided--;
         results[inst] = MI355SAT_INTERRUPTED;
         winner[inst] = -1;
         dropped[inst] = 0;
         if (cores) core_flag[inst].assign(n_assumps, 0);
+    }
+    // An open instance gets its verdict, from `worker` (-1: from no search).
+    void decide(uint32_t inst, int32_t verdict, int32_t worker) { results[inst] = verdict; winner[inst] = worker; decided++; }
+    // The caller withdraws an instance / takes it up again: true if that changes what there is to search.  Only an open
+    // instance is withdrawn, only one withdrawn without a verdict comes back - as UNSAT at once, and counted as before,
+    // if the formula itself has fallen meanwhile.
+    bool withdraw(uint32_t inst) {
+        if (!is_open(inst)) return false;
+        dropped[inst] = 1;
+        decided++;
+        return true;
+    }
+    bool reopen(uint32_t inst) {
+        if (!dropped[inst] || results[inst] != MI355SAT_INTERRUPTED) return false;
+        dropped[inst] = 0;
+        if (formula_unsat) { results[inst] = MI355SAT_UNSAT; return false; }
+        decided--;
+        return true;
     }
     // A sweep over n instances begins (assump_off: the caller's lists): nothing decided, no kernel time, no counters
     // taken over.  `cores` is the caller's to set before, `split` and the per-worker arrays (place_workers) follow once
@@ -1917,14 +1962,50 @@ struct Sweep {
         ramp_ms = 0;
         counters0.clear();
         conflicts0 = 0;
-        results.resize(n);
-        winner.resize(n);
-        dropped.resize(n);
+        results.assign(n, MI355SAT_INTERRUPTED);
+        winner.assign(n, -1);
+        dropped.assign(n, 0);
         core_flag.assign(cores ? n : 0, {});
         for (uint32_t i = 0; i < n; i++) pose(i, assump_off[i + 1] - assump_off[i]);
     }
-    // Worker w of W starts on instance w % n_instances, its cube that instance's list (base_assump / base_off); with cube
-    // splitting only the first worker of an instance is busy, the others wait for a cube to steal.
+
+    // ---- a worker: busy on a cube of its instance (running, or finished with a status sweep_step has yet to take), or
+    // idle (parked on the device, or finished and read).  Only assign / idle / close_cube / park / place_workers write w_inst,
+    // w_busy, w_cube, w_conf0 and open.
+    std::vector<int32_t> base_cube(uint32_t inst) const {      // the instance's own list: the cube of its whole search space
+        return std::vector<int32_t>(base_assump.begin() + base_off[inst], base_assump.begin() + base_off[inst + 1]);
+    }
+    bool holds_model(uint32_t w) const { return model_holder(results, winner, (uint32_t)w_inst[w]) == (int32_t)w; }
+    // Worker w is busy on `cube` of instance inst from now on.  u (null: the device has it already, as at the start)
+    // takes the record: the list and MS_ST_RUNNING, with `restart` from level 0 and its conflicts on the cube counted anew.
+    void assign(uint32_t w, uint32_t inst, std::vector<int32_t> cube, int32_t restart, WorkerUpdates* u) {
+        if (w_busy[w]) open[w_inst[w]]--;
+        w_inst[w] = (int32_t)inst;
+        w_busy[w] = 1;
+        w_cube[w] = std::move(cube);
+        open[inst]++;
+        if (w < sts.size()) {                    // (not before the first slice: nothing is gathered yet)
+            if (restart) w_conf0[w] = sts[w].conflicts;
+            sts[w].status = MS_ST_RUNNING;
+        }
+        if (u) u->add(w, MS_ST_RUNNING, restart, w_cube[w]);
+    }
+    void idle(uint32_t w) {
+        if (w_busy[w]) open[w_inst[w]]--;
+        w_busy[w] = 0;
+        w_cube[w].clear();
+    }
+    // Worker w came back MS_ST_REFUTED / MS_ST_UNSAT and sweep_step has read that: its cube is closed.
+    void close_cube(uint32_t w) { idle(w); n_closed++; }
+    // Worker w gives up its cube; a running one hears MS_ST_PARKED (a finished one keeps its status on the device).
+    void park(uint32_t w, WorkerUpdates& u) {
+        idle(w);
+        if (sts[w].status != MS_ST_RUNNING) return;
+        u.add(w, MS_ST_PARKED, 0, {});
+        sts[w].status = MS_ST_PARKED;
+    }
+    // Worker w of W starts on instance w % n_instances, its cube that instance's list; with cube splitting only the first
+    // worker of an instance is busy, the others wait for a cube to steal.
     void place_workers(uint32_t W) {
         w_inst.assign(W, 0);
         w_cube.assign(W, {});
@@ -1933,56 +2014,39 @@ struct Sweep {
         open.assign(n_instances, 0);
         for (uint32_t w = 0; w < W; w++) {
             const uint32_t inst = w % n_instances;
-            w_inst[w] = (int32_t)inst;
-            if (split && w >= n_instances) continue;
-            w_busy[w] = 1;
-            w_cube[w].assign(base_assump.begin() + base_off[inst], base_assump.begin() + base_off[inst + 1]);
-            open[inst]++;
+            if (split && w >= n_instances) w_inst[w] = (int32_t)inst;
+            else assign(w, inst, base_cube(inst), 0, nullptr);
         }
     }
 };
 
-// What the host tells workers between two slices, for ms_assign_kernel to apply: a new status, a restart request and a
-// new assumption list (the worker's cube) each.
-struct WorkerUpdates {
-    std::vector<int32_t> upd, data;
-    // The record as ms_assign_kernel reads it, five words: worker, status, restart request, the length of its assumption
-    // list and where that starts in the launch's data buffer.
-    void add_at(uint32_t w, int32_t status, int32_t restart, size_t n, size_t at) {
-        upd.insert(upd.end(), {(int32_t)w, status, restart, (int32_t)n, (int32_t)at});
-    }
-    void add(uint32_t w, int32_t status, int32_t restart, const std::vector<int32_t>& cube) {   // the list travels in `data`
-        add_at(w, status, restart, cube.size(), data.size());
-        data.insert(data.end(), cube.begin(), cube.end());
-    }
-    // Nothing to tell: no upload, no launch.  resident (warm_begin, its one user): the lists are on the device already and
-    // more follows on the stream - no `data`, no wait.
-    void send(mi355sat& s, Sweep& sw, const int32_t* resident = nullptr) {
-        if (upd.empty()) return;
-        // One record per worker: the records of a launch are applied by workgroups in no particular order, so of two for
-        // one worker (parked because its instance was decided and handed a stolen cube in the same pass of schedule_cubes;
-        // woken and moved on in one pass of rebalance_workers) either could come last.  The later one holds, a restart
-        // request of either stays.
-        {
-            std::vector<int32_t> last;
-            std::vector<size_t> at_of;     // worker -> its record in `last`, + 1
-            for (size_t r = upd.size() / 5; r-- > 0;) {
-                const size_t w = (size_t)upd[5 * r];
-                if (w >= at_of.size()) at_of.resize(w + 1, 0);
-                if (at_of[w]) { last[at_of[w] - 1 + 2] |= upd[5 * r + 2]; continue; }
-                at_of[w] = last.size() + 1;
-                last.insert(last.end(), upd.begin() + 5 * r, upd.begin() + 5 * r + 5);
-            }
-            upd.swap(last);
+// Nothing to tell: no upload, no launch.  resident (warm_begin, its one user): the lists are on the device already and
+// more follows on the stream - no `data`, no wait.
+inline void WorkerUpdates::send(mi355sat& s, Sweep& sw, const int32_t* resident) {
+    if (upd.empty()) return;
+    // One record per worker: the records of a launch are applied by workgroups in no particular order, so of two for
+    // one worker (parked because its instance was decided and handed a stolen cube in the same pass of schedule_cubes;
+    // woken and moved on in one pass of rebalance_workers) either could come last.  The later one holds, a restart
+    // request of either stays.
+    {
+        std::vector<int32_t> last;
+        std::vector<size_t> at_of;     // worker -> its record in `last`, + 1
+        for (size_t r = upd.size() / 5; r-- > 0;) {
+            const size_t w = (size_t)upd[5 * r];
+            if (w >= at_of.size()) at_of.resize(w + 1, 0);
+            if (at_of[w]) { last[at_of[w] - 1 + 2] |= upd[5 * r + 2]; continue; }
+            at_of[w] = last.size() + 1;
+            last.insert(last.end(), upd.begin() + 5 * r, upd.begin() + 5 * r + 5);
         }
-        const uint32_t n = (uint32_t)(upd.size() / 5);
-        sw.d_upd.upload(upd, s.stream);
-        if (!resident) sw.d_data.upload_nonempty(data, s.stream);
-        hipLaunchKernelGGL(ms_assign_kernel, dim3(n), dim3(64), 0, s.stream, s.L, s.d_slabs.p, n, sw.d_upd.p, resident ? resident : sw.d_data.p);
-        HIPCHK(hipGetLastError());
-        if (!resident) HIPCHK(hipStreamSynchronize(s.stream));
+        upd.swap(last);
     }
-};
+    const uint32_t n = (uint32_t)(upd.size() / 5);
+    sw.d_upd.upload(upd, s.stream);
+    if (!resident) sw.d_data.upload_nonempty(data, s.stream);
+    hipLaunchKernelGGL(ms_assign_kernel, dim3(n), dim3(64), 0, s.stream, s.L, s.d_slabs.p, n, sw.d_upd.p, resident ? resident : sw.d_data.p);
+    HIPCHK(hipGetLastError());
+    if (!resident) HIPCHK(hipStreamSynchronize(s.stream));
+}
 
 // Caller's assumption lists -> device literals: equivalent-literal substitution, then the device's variable order (perm);
 // each literal at most once per instance (a repeated assumption would open a level of its own: a list longer than n_vars
@@ -2011,6 +2075,18 @@ void map_assumptions(const mi355sat& s, const std::vector<uint32_t>& perm, uint3
 inline uint32_t fleet_size(const mi355sat& s) {      // opts.workers, or the default by formula size (sweep_begin)
     return s.opts.workers > 0 ? (uint32_t)s.opts.workers
                               : (s.offs.size() > 100000 ? MS_SEARCH_WAVES_PER_SIMD * 1024u : (s.offs.size() > 20000 ? 1024u : 256u));
+}
+
+// Ramp-up: a worker alone on its CU runs ~3x faster than one of 16, and an easy instance is decided by ONE
+// worker's few hundred conflicts - so the first 100 ms of kernel time go to one worker per CU, the next
+// 300 ms to four, and only a search that is still open after that gets the whole fleet.  (Measured: rect
+// 32x32 k=120 0.167 -> 0.088 s; 250 / 1000 ms thresholds gain nothing more at 64x64 - a worker there is bound
+// by DRAM latency even when alone - and delay the rect 24x24 ladder by 0.5-1 s.)
+// How many of `fleet` workers the next slice runs - and need a slab - a whole number per instance.
+uint32_t ramp_target(const mi355sat& s, const Sweep& sw, uint32_t fleet) {
+    if (s.opts.ramp < 0 || sw.split || s.opts.deterministic > 0) return fleet;
+    const uint32_t n = sw.n_instances, want = sw.ramp_ms < 100.f ? 256u : (sw.ramp_ms < 400.f ? 1024u : fleet);
+    return std::min(fleet, std::max(want, n) / n * n);
 }
 
 // keep (may be null): caller's literals whose variables must survive the simplification besides the assumptions' - lists
@@ -2047,8 +2123,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     sw.reset(n_instances, stop_at_first, assump_off);
     s.ph.on_device = false;              // (the mapping of the hints on the device was the last upload's)
     if (P.unsat) {
-        std::fill(sw.results.begin(), sw.results.end(), MI355SAT_UNSAT);
-        sw.decided = n_instances;
+        for (uint32_t i = 0; i < n_instances; i++) sw.decide(i, MI355SAT_UNSAT, -1);
         s.trivially_unsat = true;
         return 0;
     }
@@ -2070,8 +2145,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
     // (a solve that may be followed by warm ones leaves room for their assumption lists)
     if (keep) max_assumps = std::max<uint32_t>(max_assumps, (uint32_t)keep->size());
     const uint32_t assump_cap = sw.split ? max_assumps + 512 : max_assumps + (sw.keep_warm ? 256u : 0u);
-    const uint32_t initial = (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) ? std::max(256u, n_instances) / n_instances * n_instances : 0;
-    upload_formula(s, P, assump_cap, 0, want, initial, s.want_learnt_cap, s.want_learnt_lit_cap, MI355SAT_ERR_HIP, s.want_pool_slack);
+    upload_formula(s, P, assump_cap, 0, want, /*initial_workers=*/ramp_target(s, sw, want), s.want_learnt_cap, s.want_learnt_lit_cap, MI355SAT_ERR_HIP, s.want_pool_slack);
     if (s.n_workers < n_instances) throw HipErr{"not enough device memory for one worker per instance"};
     s.n_workers = s.n_workers / n_instances * n_instances;
     s.n_alloc = std::min(s.n_alloc, s.n_workers);
@@ -2113,13 +2187,11 @@ void schedule_cubes(mi355sat& s, Sweep& sw) {
     WorkerUpdates u;
     std::vector<uint32_t> idle, victims;
     for (uint32_t w = 0; w < W; w++) {
-        const bool undecided = sw.results[sw.w_inst[w]] == MI355SAT_INTERRUPTED;
-        if (sw.w_busy[w] && !undecided) {   // its instance was decided by someone else: park it
-            sw.w_busy[w] = 0;
-            if (sw.sts[w].status == MS_ST_RUNNING) { sw.w_cube[w].clear(); u.add(w, MS_ST_PARKED, 0, sw.w_cube[w]); sw.sts[w].status = MS_ST_PARKED; }
-        }
-        const bool keeps_model = sw.results[sw.w_inst[w]] == MI355SAT_SAT && sw.winner[sw.w_inst[w]] == (int32_t)w;
-        if (!sw.w_busy[w]) { if (!keeps_model) idle.push_back(w); }   // (mi355sat_sweep_model_of / _sweep_end read the winner's slab)
+        // Its instance was decided by someone else: parked, whatever its own status - nobody wants that any more.  (Here
+        // the two parks differ for a reason: rebalance_workers leaves a FINISHED worker its cube, whose verdict sweep_step
+        // takes once the instance is open again.  That only this one cleared the cube was an accident: nothing reads it.)
+        if (sw.w_busy[w] && sw.results[sw.w_inst[w]] != MI355SAT_INTERRUPTED) sw.park(w, u);
+        if (!sw.w_busy[w]) { if (!sw.holds_model(w)) idle.push_back(w); }
         else if (sw.sts[w].status == MS_ST_RUNNING && sw.sts[w].n_split > 0) victims.push_back(w);
     }
     // hardest cubes first: most conflicts spent on the current cube
@@ -2135,27 +2207,22 @@ void schedule_cubes(mi355sat& s, Sweep& sw) {
             if (taken[v] != round || (int32_t)round >= sw.sts[v].n_split) continue;
             if (sw.w_cube[v].size() + 1 > cap) continue;
             const int32_t d = sw.sts[v].split[round];
-            const uint32_t t = idle[next_idle++];
-            sw.w_cube[t] = sw.w_cube[v];
-            sw.w_cube[t].push_back(d ^ 1);
-            sw.w_cube[v].push_back(d);
-            sw.w_inst[t] = sw.w_inst[v];
-            sw.w_busy[t] = 1;
-            sw.w_conf0[t] = sw.sts[t].conflicts;
-            sw.open[sw.w_inst[v]]++;
+            const uint32_t inst = (uint32_t)sw.w_inst[v];
+            std::vector<int32_t> cube = sw.w_cube[v];
+            cube.push_back(d ^ 1);
+            sw.assign(idle[next_idle++], inst, cube, /*restart=*/1, &u);
+            cube.back() = d;
+            sw.assign(v, inst, cube, 0, nullptr);     // (its record follows once, with all it has given away)
             sw.n_splits++;
             taken[v] = round + 1;
-            u.add(t, MS_ST_RUNNING, 1, sw.w_cube[t]);
             any = true;
         }
         if (!any) break;
     }
     for (uint32_t v : victims)
-        if (taken[v]) u.add(v, MS_ST_RUNNING, 0, sw.w_cube[v]);
+        if (taken[v]) sw.assign(v, (uint32_t)sw.w_inst[v], sw.w_cube[v], 0, &u);
     u.send(s, sw);
 }
-
-inline bool inst_open(const Sweep& sw, uint32_t inst) { return sw.results[inst] == MI355SAT_INTERRUPTED && !sw.dropped[inst]; }
 
 // Portfolio mode, between two slices: the workers of instances that are decided (or withdrawn) move to
 // the open instances with the fewest workers.  They keep their learnt clauses (consequences of the
@@ -2168,32 +2235,22 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
     for (uint32_t w = 0; w < s.n_alloc; w++) {   // (a worker without a slab yet is picked up after grow_workers)
         const uint32_t inst = (uint32_t)sw.w_inst[w];
         const int st = sw.sts[w].status;
-        if (!all && inst_open(sw, inst)) {
+        if (!all && sw.is_open(inst)) {
             // parked when its instance was withdrawn (opts.rebalance = -1, or nothing was open), and the instance is open
             // again: back to its own list, from level 0.  Not a migration - it holds with rebalancing off too.  (A worker
             // that FINISHED its withdrawn instance - MS_ST_SAT, MS_ST_REFUTED - stays as it is: sweep_step takes its verdict.)
-            if (st == MS_ST_PARKED) {
-                sw.w_busy[w] = 1;
-                sw.w_cube[w].assign(sw.base_assump.begin() + sw.base_off[inst], sw.base_assump.begin() + sw.base_off[inst + 1]);
-                u.add(w, MS_ST_RUNNING, 1, sw.w_cube[w]);
-                sw.sts[w].status = MS_ST_RUNNING;
-            }
+            if (st == MS_ST_PARKED) sw.assign(w, inst, sw.base_cube(inst), /*restart=*/1, &u);
             if (sw.sts[w].status == MS_ST_RUNNING) cnt[inst]++;
             continue;
         }
-        if (!all && sw.winner[inst] == (int32_t)w && sw.results[inst] == MI355SAT_SAT) continue;   // keeps the model
+        if (!all && sw.holds_model(w)) continue;
         if (st == MS_ST_RUNNING || st == MS_ST_SAT || st == MS_ST_REFUTED || st == MS_ST_PARKED) movable.push_back(w);
     }
     std::vector<uint32_t> open;
-    for (uint32_t i = 0; i < n_instances; i++) if (inst_open(sw, i)) open.push_back(i);
-    auto park = [&](uint32_t w) {
-        if (sw.sts[w].status != MS_ST_RUNNING) return;
-        u.add(w, MS_ST_PARKED, 0, {});
-        sw.sts[w].status = MS_ST_PARKED;
-        sw.w_busy[w] = 0;
-    };
+    for (uint32_t i = 0; i < n_instances; i++) if (sw.is_open(i)) open.push_back(i);
     if (open.empty() || (s.opts.rebalance < 0 && !all)) {
-        for (uint32_t w : movable) park(w);
+        for (uint32_t w : movable)      // (only what runs: a finished worker keeps cube and status - see schedule_cubes)
+            if (sw.sts[w].status == MS_ST_RUNNING) sw.park(w, u);
     } else {
         // Each open instance's share of the fleet follows its weight (mi355sat_sweep_set_weights; default equal).
         // Workers of instances well above their share (> 25 % and > 2 workers) are taken off them too - highest
@@ -2210,7 +2267,7 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
                 if (cnt[i] > target[i] * 1.25 + 2) surplus[i] = cnt[i] - (uint32_t)target[i];
             for (uint32_t w = s.n_alloc; w-- > 0;) {
                 const uint32_t inst = (uint32_t)sw.w_inst[w];
-                if (!inst_open(sw, inst) || !surplus[inst] || sw.sts[w].status != MS_ST_RUNNING || cnt[inst] <= 1) continue;
+                if (!sw.is_open(inst) || !surplus[inst] || sw.sts[w].status != MS_ST_RUNNING || cnt[inst] <= 1) continue;
                 surplus[inst]--;
                 cnt[inst]--;
                 movable.push_back(w);
@@ -2234,11 +2291,7 @@ void rebalance_workers(mi355sat& s, Sweep& sw, bool all = false) {
                 if (need > best_need) { best_need = need; best = i; }
             }
             cnt[best]++;
-            sw.w_inst[w] = (int32_t)best;
-            sw.w_busy[w] = 1;
-            sw.w_cube[w].assign(sw.base_assump.begin() + sw.base_off[best], sw.base_assump.begin() + sw.base_off[best + 1]);
-            u.add(w, MS_ST_RUNNING, 1, sw.w_cube[w]);
-            sw.sts[w].status = MS_ST_RUNNING;
+            sw.assign(w, best, sw.base_cube(best), /*restart=*/1, &u);
             sw.n_moved++;
         }
     }
@@ -2378,8 +2431,7 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
     I.info.attached_units += units;
     if (empty_clause) {
         I.refuted = true;
-        sw.results[0] = MI355SAT_UNSAT;
-        sw.decided = 1;
+        sw.decide(0, MI355SAT_UNSAT, -1);
         return MI355SAT_COLD_NONE;
     }
     // the assumption list: to every resident worker now, and where grow_workers takes it from for the workers it creates
@@ -2399,10 +2451,9 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
     for (const MsState& st : sts) {
         if (st.status == MS_ST_ERR_INTERNAL) throw HipErr{status_text(st.status)};
         if (st.status < 0) { sw.active = false; return MI355SAT_COLD_DEVICE_FULL; }
-        if (st.status == MS_ST_UNSAT && sw.decided == 0) {      // a new clause is false under the level-0 facts
+        if (st.status == MS_ST_UNSAT && sw.is_open(0)) {      // a new clause is false under the level-0 facts
             I.refuted = true;
-            sw.results[0] = MI355SAT_UNSAT;
-            sw.decided = 1;
+            sw.decide(0, MI355SAT_UNSAT, -1);
         }
     }
     sw.sts = sts;
@@ -2410,42 +2461,12 @@ int warm_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const
     return MI355SAT_COLD_NONE;
 }
 
-// One slice of the search kernel over all workers.  Returns 0 or a negative error.
-int sweep_step(mi355sat& s, Sweep& sw) {
-    if (!sw.active) return 0;
-    const uint32_t n_instances = sw.n_instances;
-    // Ramp-up: a worker alone on its CU runs ~3x faster than one of 16, and an easy instance is decided by ONE
-    // worker's few hundred conflicts - so the first 100 ms of kernel time go to one worker per CU, the next
-    // 300 ms to four, and only a search that is still open after that gets the whole fleet.  (Measured: rect
-    // 32x32 k=120 0.167 -> 0.088 s; 250 / 1000 ms thresholds gain nothing more at 64x64 - a worker there is bound
-    // by DRAM latency even when alone - and delay the rect 24x24 ladder by 0.5-1 s.)
-    uint32_t active = s.n_workers;
-    if (s.opts.ramp >= 0 && !sw.split && s.opts.deterministic <= 0) {
-        const uint32_t want = sw.ramp_ms < 100.f ? 256u : (sw.ramp_ms < 400.f ? 1024u : s.n_workers);
-        active = std::min(s.n_workers, std::max(want, n_instances) / n_instances * n_instances);
-    }
-    if (active > s.n_alloc) {
-        const uint32_t had = s.n_alloc;
-        grow_workers(s, n_instances, active);
-        // the new workers start on instance w % n_instances - which may be decided or withdrawn by now: move them before the slice
-        if (n_instances > 1 && !sw.split && s.n_alloc > had && !sw.sts.empty() && (sw.decided > 0 || std::count(sw.dropped.begin(), sw.dropped.end(), 1) > 0)) {
-            sw.sts.resize(s.n_workers, MsState{});
-            rebalance_workers(s, sw);
-        }
-        // (warm incremental solve) workers fresh from the template know the uploaded formula only: everything attached since
-        if (sw.keep_warm && s.n_alloc > had && s.inc.offs.size() > 1) attach_clauses(s, had, s.n_alloc, 0, (uint32_t)(s.inc.offs.size() - 1));
-    }
-    // default slice length: 20 ms while a solve is young (easy bounds are decided within a few), 50 ms after one second
-    // and 100 ms after ten of kernel time - the host's share per slice (collecting states, the caller's loop) was a
-    // quarter of the wall-clock of the rect 26x26 ladder with 10 ms slices
-    const int auto_ms = sw.ramp_ms < 1000.f ? 20 : (sw.ramp_ms < 10000.f ? 50 : 100);
-    SliceResult sr = launch_slice(s, 0, /*stop_on_any=*/n_instances == 1 || sw.stop_at_first, /*done_on_refuted=*/!sw.split, active, auto_ms);
-    sw.ramp_ms += sr.ms;
-    proof_drain(s);
-    gather_states(s, sw.sts);
+// What the slice just gathered decided: closes the cubes of the workers that came back refuted and gives the open
+// instances their verdicts.  fw receives the refuted workers whose failed assumptions are wanted (final_cores).  Returns 0
+// or the error of a worker whose stores are full.
+int collect_verdicts(mi355sat& s, Sweep& sw, std::vector<int32_t>& fw) {
     int rc = 0;
     uint64_t confl = 0;
-    std::vector<int32_t> fw;     // refuted workers whose failed assumptions are wanted (final_cores)
     for (uint32_t w = 0; w < s.n_workers; w++) {
         const MsState& st = sw.sts[w];
         confl += st.conflicts;
@@ -2456,48 +2477,102 @@ int sweep_step(mi355sat& s, Sweep& sw) {
         // is not touched by a slice): the cube is closed, and the verdict taken, at the first step after mi355sat_sweep_reopen.
         if (st.status == MS_ST_UNSAT) sw.formula_unsat = true;
         else if (sw.dropped[inst]) continue;
-        if (st.status == MS_ST_REFUTED || st.status == MS_ST_UNSAT) {   // this worker's cube is closed
-            sw.w_busy[w] = 0;
-            sw.open[inst]--;
-            sw.n_closed++;
-        }
+        if (st.status == MS_ST_REFUTED || st.status == MS_ST_UNSAT) sw.close_cube(w);
         if (st.status == MS_ST_UNSAT) {   // refuted without any decision: the formula itself, whatever the assumptions
-            for (uint32_t i = 0; i < n_instances; i++)
-                if (inst_open(sw, i)) {
-                    sw.results[i] = MI355SAT_UNSAT; sw.winner[i] = (int32_t)w; sw.decided++;
+            for (uint32_t i = 0; i < sw.n_instances; i++)
+                if (sw.is_open(i)) {
+                    sw.decide(i, MI355SAT_UNSAT, (int32_t)w);
                     if (sw.cores) std::fill(sw.core_flag[i].begin(), sw.core_flag[i].end(), 0);   // the empty core
                 }
             continue;
         }
-        if (!inst_open(sw, inst)) continue;
+        if (!sw.is_open(inst)) continue;
         // with splitting every closed cube contributes to its instance's core, without it the deciding worker alone
         if (sw.cores && st.status == MS_ST_REFUTED) fw.push_back((int32_t)w);
-        if (st.status == MS_ST_SAT) { sw.results[inst] = MI355SAT_SAT; sw.winner[inst] = (int32_t)w; sw.decided++; }
-        else if (st.status == MS_ST_UNSAT || (st.status == MS_ST_REFUTED && (!sw.split || sw.open[inst] == 0))) {
-            // the formula itself refuted, or (with splitting) the last open cube of the instance closed;
-            // without splitting every worker holds the instance's whole search space
-            sw.results[inst] = MI355SAT_UNSAT; sw.winner[inst] = (int32_t)w; sw.decided++;
-        }
+        if (st.status == MS_ST_SAT) sw.decide(inst, MI355SAT_SAT, (int32_t)w);
+        // (with splitting) the last open cube of the instance closed; without it every worker holds the whole search space
+        else if (st.status == MS_ST_REFUTED && (!sw.split || sw.open[inst] == 0)) sw.decide(inst, MI355SAT_UNSAT, (int32_t)w);
     }
     sw.conflicts = confl - sw.conflicts0;
-    if (s.opts.verbose) {
-        uint64_t props = 0, nl = 0, busy = 0, viv = 0, vivl = 0;
-        for (auto& st : sw.sts) { props += st.propagations; nl += st.n_learnts; viv += st.n_vivified; vivl += st.n_viv_lits; }
-        if (viv) fprintf(stderr, "[mi355sat] vivified %llu clauses, %llu literals removed\n", (unsigned long long)viv, (unsigned long long)vivl);
-        for (auto b : sw.w_busy) busy += b;
-        fprintf(stderr, "[mi355sat] slice: decided %u/%u conflicts=%llu props=%llu kernel=%.3fs busy=%llu/%u splits=%llu closed=%llu kept=%llu\n",
-                sw.decided, n_instances, (unsigned long long)confl, (unsigned long long)props, s.stats.kernel_seconds,
-                (unsigned long long)busy, s.n_workers, (unsigned long long)sw.n_splits, (unsigned long long)sw.n_closed,
-                (unsigned long long)nl);
+    return rc;
+}
+
+void report_slice(const mi355sat& s, const Sweep& sw) {      // opts.verbose
+    uint64_t confl = 0, props = 0, nl = 0, busy = 0, viv = 0, vivl = 0;
+    for (auto& st : sw.sts) { confl += st.conflicts; props += st.propagations; nl += st.n_learnts; viv += st.n_vivified; vivl += st.n_viv_lits; }
+    if (viv) fprintf(stderr, "[mi355sat] vivified %llu clauses, %llu literals removed\n", (unsigned long long)viv, (unsigned long long)vivl);
+    for (auto b : sw.w_busy) busy += b;
+    fprintf(stderr, "[mi355sat] slice: decided %u/%u conflicts=%llu props=%llu kernel=%.3fs busy=%llu/%u splits=%llu closed=%llu kept=%llu\n",
+            sw.decided, sw.n_instances, (unsigned long long)confl, (unsigned long long)props, s.stats.kernel_seconds,
+            (unsigned long long)busy, s.n_workers, (unsigned long long)sw.n_splits, (unsigned long long)sw.n_closed,
+            (unsigned long long)nl);
+}
+
+// What must hold between two slices, whatever the caller did: O(workers + instances), nothing next to a slice and its
+// gather_states.  A violation is a slip of the bookkeeping above and would show slices later as a stall or a lost verdict.
+int sweep_consistent(mi355sat& s, const Sweep& sw) {
+    const char* bad = nullptr;
+    uint32_t not_open = 0;
+    std::vector<uint32_t> busy(sw.n_instances, 0);
+    for (uint32_t i = 0; i < sw.n_instances; i++) {
+        not_open += sw.is_open(i) ? 0 : 1;
+        const int32_t win = sw.winner[i];
+        if (sw.results[i] == MI355SAT_INTERRUPTED ? win != -1 : win < -1 || win >= (int32_t)sw.w_inst.size()) bad = "an instance's winner";
+        else if (sw.dropped[i] && sw.results[i] != MI355SAT_INTERRUPTED) bad = "a verdict on a withdrawn instance";
+        else if (sw.results[i] == MI355SAT_SAT && (win < 0 || (uint32_t)sw.w_inst[win] != i)) bad = "a model's worker moved on";
     }
+    if (sw.decided != not_open) bad = "the count of decided instances";
+    for (size_t w = 0; w < sw.w_inst.size() && sw.active; w++) {
+        if ((uint32_t)sw.w_inst[w] >= sw.n_instances) { bad = "a worker's instance"; break; }
+        if (sw.w_busy[w]) busy[sw.w_inst[w]]++;
+        else if (!sw.w_cube[w].empty()) bad = "an idle worker's cube";
+    }
+    for (uint32_t i = 0; i < sw.n_instances && sw.active && !bad; i++)
+        if (sw.open[i] != busy[i]) bad = "an instance's busy workers";
+    if (!bad) return 0;
+    s.err = std::string("device solver internal error (sweep bookkeeping: ") + bad + ")";
+    return MI355SAT_ERR_STATE;
+}
+
+// One slice of the search kernel over all workers.  Returns 0 or a negative error.
+int sweep_step(mi355sat& s, Sweep& sw) {
+    if (!sw.active) return 0;
+    const uint32_t n_instances = sw.n_instances;
+    // 1. ramp-up: the fleet of this slice, and slabs for it
+    const uint32_t active = ramp_target(s, sw, s.n_workers);
+    if (active > s.n_alloc) {
+        const uint32_t had = s.n_alloc;
+        grow_workers(s, n_instances, active);
+        // the new workers start on instance w % n_instances - which may be decided or withdrawn by now: move them before the slice
+        if (n_instances > 1 && !sw.split && s.n_alloc > had && !sw.sts.empty() && sw.decided > 0) {
+            sw.sts.resize(s.n_workers, MsState{});
+            rebalance_workers(s, sw);
+        }
+        // (warm incremental solve) workers fresh from the template know the uploaded formula only: everything attached since
+        if (sw.keep_warm && s.n_alloc > had && s.inc.offs.size() > 1) attach_clauses(s, had, s.n_alloc, 0, (uint32_t)(s.inc.offs.size() - 1));
+    }
+    // 2. launch.  Default slice length: 20 ms while a solve is young (easy bounds are decided within a few), 50 ms after one
+    // second and 100 ms after ten of kernel time - the host's share per slice (collecting states, the caller's loop) was a
+    // quarter of the wall-clock of the rect 26x26 ladder with 10 ms slices
+    const int auto_ms = sw.ramp_ms < 1000.f ? 20 : (sw.ramp_ms < 10000.f ? 50 : 100);
+    SliceResult sr = launch_slice(s, 0, /*stop_on_any=*/n_instances == 1 || sw.stop_at_first, /*done_on_refuted=*/!sw.split, active, auto_ms);
+    sw.ramp_ms += sr.ms;
+    // 3. drain, gather, collect
+    proof_drain(s);
+    gather_states(s, sw.sts);
+    std::vector<int32_t> fw;
+    int rc = collect_verdicts(s, sw, fw);
+    if (s.opts.verbose) report_slice(s, sw);
     if (rc) return rc;
-    if (!fw.empty() && (rc = final_cores(s, sw, fw)) != 0) return rc;   // before any slab's assumptions are rewritten below
+    // 4. cores - before any slab's assumptions are rewritten below - and who works on what in the next slice
+    if (!fw.empty() && (rc = final_cores(s, sw, fw)) != 0) return rc;
     HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
-    if (sw.decided == n_instances || (sw.stop_at_first && sw.decided > 0)) return 0;
-    if (sw.split) schedule_cubes(s, sw);
-    else if (n_instances > 1 && (sw.decided > 0 || sw.weights_dirty)) rebalance_workers(s, sw);
-    sw.weights_dirty = false;
-    return 0;
+    if (sw.decided < n_instances && !(sw.stop_at_first && sw.decided > 0)) {
+        if (sw.split) schedule_cubes(s, sw);
+        else if (n_instances > 1 && (sw.decided > 0 || sw.weights_dirty)) rebalance_workers(s, sw);
+        sw.weights_dirty = false;
+    }
+    return sweep_consistent(s, sw);
 }
 
 bool sweep_finished(const mi355sat& s, const Sweep& sw) {
@@ -2523,6 +2598,24 @@ void sweep_end(mi355sat& s, Sweep& sw) {
     } else if (sw.active) accumulate_stats(s, sw.sts);
     sw.active = false;
     consume_interrupt(s);
+}
+
+// The model of instance inst from the slab of the worker that found it; false if the instance is not SAT.
+bool fetch_model_of(mi355sat& s, const std::vector<int32_t>& results, const std::vector<int32_t>& winner, uint64_t inst, std::vector<int8_t>& out) {
+    const int32_t w = model_holder(results, winner, inst);
+    if (w >= 0) fetch_model(s, (uint32_t)w, out, s.max_var);
+    return w >= 0;
+}
+
+// After the caller withdrew or reopened instances (changed: that made a difference): the workers of what is no longer
+// open move on, parked workers and those of decided instances take up what is open again.  Not with cube splitting,
+// where a withdrawn instance's cubes are searched on.
+int reschedule_after_caller(mi355sat& s, Sweep& sw, bool changed) {
+    if (changed && sw.active && !sw.split) {
+        if (sw.sts.size() != s.n_workers) gather_states(s, sw.sts);
+        rebalance_workers(s, sw);
+    }
+    return sweep_consistent(s, sw);
 }
 
 // cores (may be null): per instance, the caller's assumptions its UNSAT answer rests on, in the caller's order (empty
@@ -2623,8 +2716,6 @@ void sweep_repose(mi355sat& s, Sweep& sw, uint32_t inst, const std::vector<int32
 // ms_assign_kernel: new assumption list, MS_ST_RUNNING, back to level 0); the lists go where grow_workers takes them
 // from for the workers the ramp-up creates later.
 void sweep_retarget(mi355sat& s, Sweep& sw) {
-    sw.decided = 0;
-    for (uint32_t i = 0; i < sw.n_instances; i++) sw.decided += inst_open(sw, i) ? 0 : 1;
     s.d_assump.upload_nonempty(sw.base_assump, s.stream);
     s.d_assump_off.upload(sw.base_off, s.stream);
     if (sw.sts.size() != s.n_workers) gather_states(s, sw.sts);
@@ -2714,7 +2805,7 @@ int minimize_search(mi355sat& s, std::vector<int32_t>& K, int64_t budget, mi355s
             if (rc) break;
         } else {
             for (uint32_t j = 0; j < m; j++) sweep_repose(s, sw, j, cand_lits[j]);
-            for (uint32_t j = m; j < N; j++) { sw.results[j] = MI355SAT_INTERRUPTED; sw.winner[j] = -1; sw.dropped[j] = 1; }
+            for (uint32_t j = m; j < N; j++) { sw.pose(j, 0); sw.withdraw(j); }     // unused this round
             sweep_retarget(s, sw);
         }
         info.rounds++;
@@ -3780,7 +3871,7 @@ int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* as
             results_out[i] = results[i];
             s->batch_cores[i].lits.swap(cores[i]);
             s->batch_cores[i].valid = results[i] == MI355SAT_UNSAT;
-            if (results[i] == MI355SAT_SAT && winner[i] >= 0) fetch_model(*s, (uint32_t)winner[i], s->batch_models[i], s->max_var);
+            fetch_model_of(*s, results, winner, i, s->batch_models[i]);
             tally_answer(*s, results[i]);
         }
         return 0;
@@ -3887,16 +3978,9 @@ int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n) {
         bool any = false;
         for (uint64_t j = 0; j < n; j++) {
             if (instances[j] >= sw.n_instances) { s->err = "instance out of range"; return MI355SAT_ERR_ARG; }
-            if (!inst_open(sw, (uint32_t)instances[j])) continue;
-            sw.dropped[instances[j]] = 1;
-            sw.decided++;
-            any = true;
+            any |= sw.withdraw((uint32_t)instances[j]);
         }
-        if (any && sw.active && !sw.split && sw.decided < sw.n_instances) {
-            if (sw.sts.size() != s->n_workers) gather_states(*s, sw.sts);
-            rebalance_workers(*s, sw);
-        }
-        return 0;
+        return reschedule_after_caller(*s, sw, any && sw.decided < sw.n_instances);     // (nothing left open: nobody moves)
     });
 }
 
@@ -3917,18 +4001,9 @@ int mi355sat_sweep_reopen(mi355sat* s, const uint64_t* instances, uint64_t n) {
         bool any = false;
         for (uint64_t j = 0; j < n; j++) {
             if (instances[j] >= sw.n_instances) { s->err = "instance out of range"; return MI355SAT_ERR_ARG; }
-            const uint64_t i = instances[j];
-            if (!sw.dropped[i] || sw.results[i] != MI355SAT_INTERRUPTED) continue;   // only what was withdrawn undecided
-            sw.dropped[i] = 0;
-            if (sw.formula_unsat) { sw.results[i] = MI355SAT_UNSAT; continue; }   // the formula is refuted: no search (it stays counted)
-            sw.decided--;
-            any = true;
+            any |= sw.reopen((uint32_t)instances[j]);
         }
-        if (any && sw.active && !sw.split) {
-            if (sw.sts.size() != s->n_workers) gather_states(*s, sw.sts);
-            rebalance_workers(*s, sw);   // parked workers and those of decided / withdrawn instances take them up
-        }
-        return 0;
+        return reschedule_after_caller(*s, sw, any);
     });
 }
 
@@ -3936,12 +4011,11 @@ int mi355sat_sweep_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_
     if (!s || !s->sweep || !out) return MI355SAT_ERR_STATE;
     return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
-        if (instance >= sw.n_instances || sw.results[instance] != MI355SAT_SAT || sw.winner[instance] < 0) {
+        std::vector<int8_t> m;
+        if (instance >= sw.n_instances || !fetch_model_of(*s, sw.results, sw.winner, instance, m)) {
             s->err = "no model for that instance";
             return MI355SAT_ERR_STATE;
         }
-        std::vector<int8_t> m;
-        fetch_model(*s, (uint32_t)sw.winner[instance], m, s->max_var);
         copy_model(m, out, n_vars);
         return 0;
     });
@@ -3952,9 +4026,7 @@ int mi355sat_sweep_end(mi355sat* s) {
     return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         s->batch_models.assign(sw.n_instances, {});
-        for (uint32_t i = 0; i < sw.n_instances; i++)
-            if (sw.results[i] == MI355SAT_SAT && sw.winner[i] >= 0)
-                fetch_model(*s, (uint32_t)sw.winner[i], s->batch_models[i], s->max_var);
+        for (uint32_t i = 0; i < sw.n_instances; i++) fetch_model_of(*s, sw.results, sw.winner, i, s->batch_models[i]);
         consume_interrupt(*s);
         delete s->sweep;
         s->sweep = nullptr;
