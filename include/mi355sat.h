@@ -605,6 +605,56 @@ int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* targ
  * (launches of about 20 ms). */
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch);
 
+/* Honour the deletion lines of a proof (on != 0) in mi355sat_check_proof / _check_proof_file / _trim_proof /
+ * _trim_proof_file and what _trim_write_drup / _trim_write_lrat write of such a trim.  A switch on the handle, off by
+ * default; off is the behaviour described above, bit for bit.  With it on a worker keeps only the lemmas that are live, so
+ * its clause store and watch pool are sized from the PEAK of the live lemmas instead of their number: proofs whose
+ * lemmas do not fit a worker's stores all at once become checkable, and a proof that uses a lemma after deleting it is
+ * found out.  The verdict stays a function of formula, proof and target alone.
+ * Resolution, on the host before anything is uploaded.  A deletion line names a clause by its literals as a set (order
+ * and repeats do not matter).  It is matched to the latest lemma line before it with the same literal set that is still
+ * live; two lemma lines with the same literals are two clauses and one deletion removes one of them.  A line without a
+ * live match that equals one of the caller's clauses is counted ignored_original and has no effect (original clauses are
+ * never deleted: sound, and the same in every worker); any other line without a match - a deletion before its lemma, a
+ * second deletion of one copy - is counted ignored_unmatched.  A match to a tautological lemma counts as honoured and
+ * does nothing: such a lemma is never attached.
+ * State.  Live: a set of lemma indices.  Facts: a set of literals that only grows.  close() sets Facts to the
+ * unit-propagation closure of originals + Live + Facts; a conflict there is refuted_at = min(.., the item in front of
+ * which it happened).
+ * Run, items in file order.  A maximal run of consecutive deletion lines in front of item j is a group: close() once,
+ * then the group's matched lemmas leave Live.  At item j: close(); lemma j is RUP iff propagating its negation over
+ * originals + Live + Facts ends in a conflict; then j joins Live (a failed lemma too, the target not; a tautology counts
+ * as RUP without joining).  Facts outlive the clauses that gave them: deleting a unit lemma, or the clause behind a
+ * level-0 fact, takes nothing back (drat-trim's default reading).  A clause that is the reason of a fact is therefore
+ * satisfied for ever, and whether a worker keeps or drops it changes no verdict: the device keeps it ("locked").
+ * valid, first_failed, refuted_at and n_lemmas keep their meaning; n_deletions_ignored = ignored_original +
+ * ignored_unmatched.  Sizes: learnt_cap = peak_live_lemmas + min(n_vars + 1, honoured lemmas) - the slack is for locked
+ * clauses, one per variable at most - and the literal store likewise with the longest of the deleted lemmas as slack; the
+ * watch pool follows learnt_cap.  A store that still fills ends the call with MI355SAT_ERR_OOM, never with a verdict.
+ * A trim keeps its formats (ids as before, no deletion lines written); a hint names a lemma the proof had deleted by
+ * then only if that lemma was locked.
+ * Measured (MI355X, profiles/r10_proof_deletions.log).  rect 16x16 k = 3, the 16-worker fleet's proof (2468
+ * lemmas, no deletion line): 0.009 s with the switch off - the parent commit's library takes the same - and 0.013 s with
+ * it on, the same slabs and 256 segments.  rect 24x24 k = 8, the fleet's proof (157 278 lemmas, 136 460 deletion lines,
+ * 150 MB; solved in 5.1 s): off, MI355SAT_ERR_OOM as before; on, valid in 4.5 s with 1024 segments, at most 22 310 lemmas
+ * live, learnt_cap 34 526, 22.6 MiB of stores and pool per worker; the trim with hints takes 10.8 s. */
+int mi355sat_proof_deletions(mi355sat* s, int on);
+typedef struct mi355sat_proof_del_info {
+    /* functions of the proof (and the caller's clauses) alone */
+    uint64_t honoured, ignored_original, ignored_unmatched;
+    uint64_t groups;                    /* maximal runs of consecutive deletion lines */
+    uint64_t peak_live_lemmas;          /* the largest Live ever gets */
+    uint64_t peak_live_words;           /* ... in literal words, each lemma (repeats dropped) rounded up to 4 as the store rounds it */
+    /* what the slabs were laid out with (0: the call needed no launch) */
+    uint64_t learnt_cap, learnt_lit_cap, pool_cap;
+    /* summed over workers: they may differ from cut to cut and from run to run, as the core of a trim does */
+    uint64_t skipped_locked;            /* deleted lemmas a worker kept: the reason of a fact when they died, or a fact from
+                                           the moment they were attached (one free literal) */
+    uint64_t compactions;               /* passes over a worker's store, one per group that names an attachable lemma */
+} mi355sat_proof_del_info;
+/* The last check or trim made with the switch on; MI355SAT_ERR_STATE before the first one. */
+int mi355sat_debug_proof_deletions(const mi355sat* s, mi355sat_proof_del_info* out);
+
 
 /* Trim a DRUP proof while it is checked: which of the caller's clauses and which lemmas the derivation of the target
  * rests on, and - with MI355SAT_TRIM_HINTS - an LRAT file that a checker without watch lists, search or GPU verifies

@@ -94,6 +94,7 @@ extern "C" {
                             out: *mut ProofInfo) -> c_int;
     fn mi355sat_trim_proof(s: *mut c_void, proof: *const i32, n_words: u64, target: *const i32, n_target: u64, segments: u32,
                            flags: u32, out: *mut TrimInfo) -> c_int;
+    fn mi355sat_proof_deletions(s: *mut c_void, on: c_int) -> c_int;
     fn mi355sat_trim_core(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_trim_lemmas(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_trim_write_lrat(s: *mut c_void, path: *const c_char) -> c_int;
@@ -178,6 +179,13 @@ impl Mi355Sat {
         };
         if rc < 0 { return Err(self.err()); }
         Ok(info)
+    }
+    /// Honour the proof's deletion lines in `check_proof` / `trim_proof` (`mi355sat_proof_deletions`; off by default:
+    /// counted and ignored).  A worker then holds only the live lemmas and its stores are sized from their peak, so long
+    /// proofs fit; a proof that uses a lemma after deleting it is not valid.  Semantics: include/mi355sat.h.
+    pub fn set_proof_deletions(&mut self, on: bool) -> anyhow::Result<()> {
+        if unsafe { mi355sat_proof_deletions(self.h, on as c_int) } < 0 { return Err(self.err()); }
+        Ok(())
     }
     /// Trimmed certificate (`mi355sat_trim_proof`): `check_proof` in the tracing build of the checker.  Where
     /// `check.valid == 1`, `trim_core` / `trim_lemmas` name the clauses of this handle (0-based, in the order they were

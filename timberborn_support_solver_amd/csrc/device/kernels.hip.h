@@ -3110,6 +3110,89 @@ DEV void rup_trace(Wk& w, const MsShared& sh, const MsLayout& L, const MsTrace& 
     used += MS_TR_REC * (1 + n_rec);
 }
 
+// ---- deletion lines honoured (mi355sat_proof_deletions, ms_rup_kernel<LV, TRACE, true>) ------
+// One pass over the learnt store in front of item j, reduce_db's shape with another rule: a slot whose lemma (the slab's
+// `remap` array: slot -> lemma) dies in front of an item <= j (death[lemma], written by the host from the resolved deletion
+// lines) goes, unless it is locked - a watched literal TRUE with this clause as its reason.  The trail holds level 0 only
+// and stands at its fixpoint, so a locked clause is satisfied for ever: keeping it changes no verdict, and rup_trace's
+// walk over the level-0 reasons stays valid.  It is counted once, at the item it dies in front of.  Kept clauses move down
+// in lc_lits / lc_lbd / wl with their remap entry; the reason and start of the variable a kept clause locks are repaired
+// as it moves (a new index is below every index still to be read, so no later lock test mistakes it); then the watch
+// lists are laid out again.  Nothing moves, and no list is rebuilt, when no slot dies.
+template <bool LV>
+DEV void rup_drop_dead(Wk& w, const MsShared& sh, const MsLayout& L, Gp<const uint32_t> death, uint32_t j, uint32_t& n_locked) {
+    Gp<MsClauseRec> lrec = WKA(MsClauseRec, wl) + sh.n_orig;
+    Gp<uint32_t> lc_lbd = WK_PTR(uint32_t, w, L, lc_lbd);
+    Gp<int32_t> lc_lits = WK_PTR(int32_t, w, L, lc_lits);
+    Gp<uint32_t> slot_lemma = WK_PTR(uint32_t, w, L, remap);
+    const uint32_t n = w.n_learnts;
+    uint32_t nk = 0, nlits = 0;
+    for (uint32_t k0 = 0; k0 < n; k0 += MS_WAVE) {
+        const uint32_t k = k0 + (uint32_t)w.lane;
+        const bool act = k < n;
+        bool dead = false, late = false;
+        uint32_t o0 = 0, len = 0, raw = 0, jl = 0;
+        int2 ww = make_int2(0, 0);
+        int lockv = -1;                 // the variable this clause is the reason of
+        if (act) {
+            raw = lc_lbd[k];
+            jl = slot_lemma[k];
+            const MsClauseRec ch = lrec[k];
+            o0 = ch.start;
+            len = ch.size;
+            ww = make_int2(ch.w0, ch.w1);
+            const int cref = (int)(sh.n_orig + k);
+            if (lit_value<LV>(w, sh, L, ww.x) == MS_VAL_TRUE && VREC[ww.x >> 1].reason == cref) lockv = ww.x >> 1;
+            else if (lit_value<LV>(w, sh, L, ww.y) == MS_VAL_TRUE && VREC[ww.y >> 1].reason == cref) lockv = ww.y >> 1;
+            const uint32_t d = death[jl];
+            dead = d <= j;
+            late = d == j;
+        }
+        n_locked += (uint32_t)popc64(ballot(late && lockv >= 0));
+        const bool keep = act && (!dead || lockv >= 0);
+        const u64 km = ballot(keep);
+        if (!keep) len = 0;
+        // exclusive prefix of (16-byte aligned) literal counts among kept clauses
+        uint32_t pre = (len + 3u) & ~3u;
+        for (int o = 1; o < MS_WAVE; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)pre, o, 64);
+            if (w.lane >= o) pre += t;
+        }
+        const uint32_t total = (uint32_t)bcast((int)pre, 63);
+        pre -= (len + 3u) & ~3u;
+        const uint32_t nkk = nk + (uint32_t)popc64(km & lanemask_lt(w.lane));
+        wave_fence();
+        // move literals (dest <= source, clause by clause inside the chunk in lane order)
+        for (int src = 0; src < MS_WAVE; src++) {
+            if (!((km >> src) & 1)) continue;
+            const uint32_t so = (uint32_t)bcast((int)o0, src), slen = (uint32_t)bcast((int)len, src);
+            const uint32_t dd = nlits + (uint32_t)bcast((int)pre, src);
+            if (dd != so)
+                for (uint32_t t = 0; t < slen; t += MS_WAVE) {
+                    const uint32_t x = t + (uint32_t)w.lane;
+                    const int lv = x < slen ? lc_lits[so + x] : 0;
+                    wave_fence();
+                    if (x < slen) lc_lits[dd + x] = lv;
+                    wave_fence();
+                }
+        }
+        if (keep) {
+            lrec[nkk] = MsClauseRec{ww.x, ww.y, nlits + pre, len};
+            lc_lbd[nkk] = raw;
+            slot_lemma[nkk] = jl;
+            if (lockv >= 0) { VREC[lockv].reason = (int)(sh.n_orig + nkk); VREC[lockv].start = nlits + pre; }
+        }
+        nk += (uint32_t)popc64(km);
+        nlits += total;
+        wave_fence();
+    }
+    if (nk == n) return;
+    w.n_learnts = nk;
+    w.lc_lits_n = nlits;
+    wave_fence();
+    rebuild_watches(w, sh, L);
+}
+
 // ---- forward RUP check of a clausal proof (mi355sat_check_proof) -------------------------
 // Lemma i of a DRUP proof must follow from the formula and the lemmas before it by unit propagation alone: assume the
 // negation of its literals, propagate, expect a conflict - this kernel's hot loop, once per lemma, and the checks of
@@ -3139,10 +3222,18 @@ DEV void rup_trace(Wk& w, const MsShared& sh, const MsLayout& L, const MsTrace& 
 // and the lemma behind a level-0 fact that was attached as a unit (j + 1 in the start word of its variable record; 0 = a
 // unit clause of the caller).  A launch also ends when the region has less room left than two items of the largest size
 // (a check and the refutation its attach may find); the host drains the regions after every launch.
-template <bool LV, bool TRACE = false>
+// DEL (mi355sat_proof_deletions): deletion lines are honoured as include/mi355sat.h defines it.  The host has resolved them:
+// death[lemma] is the item in front of which the lemma dies (UINT32_MAX: never), and bit 1 of skip[j] says that a group of
+// deletion lines stands in front of item j.  The level-0 trail is the set of facts, which only grows.  At a group EVERY
+// worker - also one that is still in its unchecked prefix - propagates the level-0 queue to its fixpoint (a fact that only
+// a lemma about to die gives must not depend on the cut; a conflict there is refuted_at = min(.., j), exact in the worker
+// that owns j) and then drops the dead slots (rup_drop_dead).  Between groups the prefix stays lazy: the closure is monotone
+// in what is added.  The slot -> lemma map is kept in both DEL builds.  Script words [8] / [9]: dead lemmas kept because
+// locked, and passes made.  DEL = false is the code above, unchanged.
+template <bool LV, bool TRACE = false, bool DEL = false>
 __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L, char* slabs, MsParams prm, const int32_t* lits,
                                                         const uint32_t* offs, const uint8_t* skip, uint32_t n_items,
-                                                        unsigned long long* mins, MsTrace tr) {
+                                                        unsigned long long* mins, MsTrace tr, const uint32_t* death) {
     __shared__ int32_t s_ring[MS_LDS_RING];
     __shared__ uint32_t s_claim[MS_CLAIM_SLOTS];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[4 * MS_MAX_GROUPS < 64 ? 64 : 4 * MS_MAX_GROUPS];
@@ -3184,6 +3275,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
     uint32_t b = (uint32_t)uni(cur[2]);
     if (b > n_items) b = n_items;
     uint32_t n_checked = 0, n_attached = 0, budget = prm.slice_conflicts;
+    uint32_t n_locked = 0, n_passes = 0;          // (DEL)
     auto note_min = [&](int which, uint32_t idx) {
         if (w.lane == 0) (void)atomicMax(&mins[which], ~(unsigned long long)idx);   // (the words hold complements)
     };
@@ -3195,15 +3287,22 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             rebuild_watches(w, sh, L);
             if (w.status != MS_ST_RUNNING) break;
         }
-        const bool skipped = uni((int)sk[j]) != 0;    // x and ~x: RUP, never attached - but index j may be where it falls
+        const int flags = uni((int)sk[j]);
+        const bool skipped = DEL ? (flags & 1) != 0 : flags != 0;    // x and ~x: RUP, never attached - but index j may be where it falls
+        const bool group = DEL && (flags & 2) != 0;   // deletion lines in front of j that name live lemmas
         const uint32_t lb = (uint32_t)uni((int)co[j]), le = (uint32_t)uni((int)co[j + 1]);
-        if (j >= a) {
+        if (j >= a || group) {
             if (propagate<LV>(w, sh, L)) {            // the level-0 queue
                 note_min(1, j);
                 w.status = MS_ST_UNSAT;
-                if (TRACE) rup_trace<LV>(w, sh, L, tr, wid, log_used, j | MS_TR_REFUTED, j, 0, 0, cl, co);
+                if (TRACE && j >= a) rup_trace<LV>(w, sh, L, tr, wid, log_used, j | MS_TR_REFUTED, j, 0, 0, cl, co);
                 break;
             }
+            if (w.status != MS_ST_RUNNING) break;
+        }
+        if (group) {
+            n_passes++;
+            rup_drop_dead<LV>(w, sh, L, (Gp<const uint32_t>)death, j, n_locked);
             if (w.status != MS_ST_RUNNING) break;
         }
         if (skipped) continue;
@@ -3248,7 +3347,12 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             j++;
             break;
         }
-        if (cnt == 1) { enqueue_uniform<LV>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE, TRACE ? j + 1 : 0u); continue; }
+        if (cnt == 1) {
+            // (DEL: a lemma that is a fact from the start takes no slot; when the proof deletes it, it is kept as locked ones are)
+            if (DEL && uni((int)((Gp<const uint32_t>)death)[j]) != -1) n_locked++;
+            enqueue_uniform<LV>(w, sh, L, uni(learnt_buf[0]), MS_REASON_NONE, TRACE ? j + 1 : 0u);
+            continue;
+        }
         {   // A list that holds a large share of the proof asks for more than the quarter of the pool the rule above keeps
             // free: if the two pushes of this clause could not both grow their lists (list_push_uniform's policy), lay the
             // lists out densely first - every list then has two free slots at least, and the dense layout always fits
@@ -3267,7 +3371,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
         }
         const int cref = add_learnt<LV>(w, sh, L, cnt, 1u | MS_LBD_NOLOG);
         if (cref < 0) break;
-        if (TRACE && w.lane == 0) WKA(uint32_t, remap)[(uint32_t)cref - sh.n_orig] = j;
+        if ((TRACE || DEL) && w.lane == 0) WKA(uint32_t, remap)[(uint32_t)cref - sh.n_orig] = j;
     }
     if (w.status == MS_ST_RUNNING && j >= b) w.status = MS_ST_SAT;
     wave_fence();
@@ -3277,6 +3381,7 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
         Gp<u64> cnt64 = (Gp<u64>)(cur + 4);
         cnt64[0] += n_checked;
         cnt64[1] += n_attached;
+        if (DEL) { cur[8] += (int32_t)n_locked; cur[9] += (int32_t)n_passes; }
     }
     wk_store<LV>(w, sh, L, __builtin_readcyclecounter() - t0);
 }

@@ -1,11 +1,12 @@
 // tbs_cli — minimal command-line driver of the solve path (NOT the reference's REPL/UI):
-//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate] [--certify PATH]
+//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions]]
 //   tbs_cli file PATH.toml [-l1:K] ...
 // Mirrors `solve -l<dims>:<n>` of crates/repl/src/main.rs:44-75,248-261: encode once, then solver_loop.
 // Ctrl-C calls mi355sat_interrupt (main.rs:297-324).
 // --certify PATH: when the loop ends on a bound that is UNSAT, that bound is solved once more with its DRUP proof written to
 // PATH, the proof is checked and trimmed on a fresh handle (mi355sat_trim_proof_file) and PATH.lrat is written: a certificate
-// that a checker of a few dozen lines verifies against the bound's CNF.
+// that a checker of a few dozen lines verifies against the bound's CNF.  --honour-deletions: the check honours the proof's
+// deletion lines (mi355sat_proof_deletions): a worker's stores hold the live lemmas only; the output gains one line.
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -17,7 +18,7 @@
 static std::atomic<mi355sat*> g_current{nullptr};
 static std::atomic<int> g_interrupted{0};
 // The UNSAT bound once more with a proof, trimmed on a fresh handle.  Returns false if the answer was not UNSAT again.
-static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::string& path) {
+static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::string& path, bool honour_deletions) {
     auto fail = [](mi355sat* s, const char* ctx) {
         const std::string m = std::string(ctx) + ": " + mi355sat_last_error(s);
         mi355sat_free(s);
@@ -39,6 +40,7 @@ static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::s
     if (mi355sat_add_cnf(s, cnf.lits.data(), cnf.offsets.data(), cnf.n_clauses()) < 0) fail(s, "Failed to add CNF");
     mi355sat_reserve(s, cnf.n_vars);
     mi355sat_trim_info info{};
+    if (honour_deletions) mi355sat_proof_deletions(s, 1);
     g_current.store(s);
     const int tr = mi355sat_trim_proof_file(s, path.c_str(), nullptr, 0, 0, MI355SAT_TRIM_HINTS, &info);
     g_current.store(nullptr);
@@ -50,6 +52,10 @@ static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::s
     }
     const std::string lrat = path + ".lrat";
     if (mi355sat_trim_write_lrat(s, lrat.c_str()) < 0) fail(s, "trim_write_lrat");
+    mi355sat_proof_del_info del{};
+    if (honour_deletions && mi355sat_debug_proof_deletions(s, &del) == 0)
+        std::cout << "Deletions: " << del.honoured << " honoured, " << del.ignored_original + del.ignored_unmatched << " ignored, at most "
+                  << del.peak_live_lemmas << " of " << info.check.n_lemmas << " lemmas live" << std::endl;
     mi355sat_free(s);
     std::cout << "Certificate: " << lrat << " - core " << info.core_clauses << " of " << cnf.n_clauses() << " clauses, "
               << info.lemmas_needed << " of " << info.check.n_lemmas << " lemmas needed (checked in " << info.check.seconds
@@ -68,7 +74,7 @@ int main(int argc, char** argv) {
     try {
         if (argc < 3) {
             fprintf(stderr, "usage: %s rect W H | file PATH [-l<dims>:<n>]... [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] "
-                            "[--verbose] [--no-simp] [--eliminate] [--certify PATH]\n", argv[0]);
+                            "[--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions]]\n", argv[0]);
             return 2;
         }
         WorldGrid grid;
@@ -82,6 +88,7 @@ int main(int argc, char** argv) {
         opts.device = -1;
         bool sweep = false, incremental = false, phase_hints = false;
         std::string certify_path;
+        bool honour_deletions = false;
         for (; a < argc; a++) {
             std::string arg = argv[a];
             if (arg.rfind("-l", 0) == 0) {             // -l<dims>:<n>, dims = AxB or A (=AxA), main.rs:120-142
@@ -105,6 +112,7 @@ int main(int argc, char** argv) {
             else if (arg == "--incremental") incremental = true;   // one warm handle for the whole ladder (mi355sat_set_incremental)
             else if (arg == "--phase-hints") phase_hints = true;   // every rung starts its search at the layout of the rung before (mi355sat_set_phases)
             else if (arg == "--certify" && a + 1 < argc) certify_path = argv[++a];
+            else if (arg == "--honour-deletions") honour_deletions = true;
             else throw std::runtime_error("unknown argument " + arg);
         }
         Encoding enc = Encoding::encode(defs, grid);
@@ -116,7 +124,7 @@ int main(int argc, char** argv) {
         if (!certify_path.empty() && !hist.empty() && hist.back().result == SolverResult::Unsat && !g_interrupted.load()) {
             PlatformLimits bound = limits;
             if (hist.back().k != (size_t)-1) bound.card_limits[Dims{1, 1}] = hist.back().k;
-            if (!certify(enc.with_limits(bound).into_cnf(), opts, certify_path)) return 1;
+            if (!certify(enc.with_limits(bound).into_cnf(), opts, certify_path, honour_deletions)) return 1;
         }
         return hist.empty() ? 1 : 0;
     } catch (const std::exception& e) {

@@ -14,8 +14,10 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <map>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <queue>
@@ -418,6 +420,9 @@ struct mi355sat {
     uint32_t core_min_round = 0;
     uint32_t proof_chunk = 0;                  // test hook (mi355sat_debug_proof_check_chunk): lemmas per worker and launch of a proof check
     uint32_t trim_log_words = 0;               // test hook (mi355sat_debug_trim_log): words per worker of a traced check's dependency log
+    bool proof_del = false;                    // mi355sat_proof_deletions: checks and trims honour the proof's deletion lines
+    bool proof_del_have = false;               // proof_del_info describes a check or trim made with the switch on
+    mi355sat_proof_del_info proof_del_info{};
     // What the last mi355sat_trim_proof found a valid proof to rest on; dropped by the next trim_proof / check_proof, a clause
     // added, a sweep begun.  Indices: caller clauses 0-based in the order they were added, lemmas 0-based, both ascending.
     struct Trim {
@@ -2916,6 +2921,10 @@ struct ProofLemmas {
     std::vector<int32_t> lits;         // DIMACS literals of all lemmas, then the target's
     std::vector<uint64_t> offs{0};     // n_lemmas + 2 entries once the target is appended
     uint64_t n_lemmas = 0, n_deletions = 0;
+    // with mi355sat_proof_deletions on: the deletion lines (DIMACS literals) and the item each stands in front of
+    bool keep_deletions = false;
+    std::vector<int32_t> del_lits;
+    std::vector<uint64_t> del_offs{0}, del_at;
 };
 
 // One check as it passes from stage to stage of check_proof_impl.
@@ -2929,6 +2938,12 @@ struct ProofCheck {
     std::vector<uint32_t> doff{0};
     std::vector<uint8_t> skip;         // per item: it holds x and ~x - true whatever the assignment, never checked
     uint64_t store_lits = 0;           // what the lemmas take in a worker's learnt store, each 16-byte aligned
+    // deletion lines honoured (proof_resolve_deletions): per lemma the item it dies in front of, per item "a group here"
+    bool del = false;
+    std::vector<uint32_t> death;
+    std::vector<uint8_t> group;
+    uint64_t lock_slack = 0, lock_slack_words = 0;   // room for dead lemmas a worker keeps because they are locked
+    DevBuf<uint32_t> d_death;
     // on the device (proof_upload): S segments of the item list, one worker each
     uint32_t S = 0;
     DevBuf<int32_t> d_lits;
@@ -2951,8 +2966,14 @@ int parse_proof_words(mi355sat& s, const int32_t* proof, uint64_t n_words, Proof
             i++;
         }
         if (i == n_words) { s.err = "proof: the last clause is not terminated"; return MI355SAT_ERR_ARG; }
-        if (del) out.n_deletions++;
-        else {
+        if (del) {
+            out.n_deletions++;
+            if (out.keep_deletions) {
+                out.del_lits.insert(out.del_lits.end(), proof + st, proof + i);
+                out.del_offs.push_back(out.del_lits.size());
+                out.del_at.push_back(out.n_lemmas);
+            }
+        } else {
             out.lits.insert(out.lits.end(), proof + st, proof + i);
             out.offs.push_back(out.lits.size());
             out.n_lemmas++;
@@ -3001,9 +3022,12 @@ SliceResult launch_rup(mi355sat& s, const ProofCheck& C, const MsTrace& mt) {
     return timed_launch(s, [&] {
         with_flag(build.lds != 0, [&](auto lds_build) {
             with_flag(mt.log != nullptr, [&](auto traced) {
-                hipLaunchKernelGGL((ms_rup_kernel<decltype(lds_build)::value, decltype(traced)::value>), dim3(active), dim3(MS_WAVE), build.dyn_lds_bytes,
-                                   s.stream, s.sh, s.L, s.d_slabs.p, prm, (const int32_t*)C.d_lits.p, (const uint32_t*)C.d_offs.p,
-                                   (const uint8_t*)C.d_skip.p, C.n_items, C.d_mins.p, mt);
+                with_flag(C.del, [&](auto deleting) {
+                    hipLaunchKernelGGL((ms_rup_kernel<decltype(lds_build)::value, decltype(traced)::value, decltype(deleting)::value>), dim3(active),
+                                       dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, (const int32_t*)C.d_lits.p,
+                                       (const uint32_t*)C.d_offs.p, (const uint8_t*)C.d_skip.p, C.n_items, C.d_mins.p, mt,
+                                       (const uint32_t*)C.d_death.p);
+                });
             });
         });
     }, [] {});
@@ -3256,6 +3280,99 @@ int proof_target(mi355sat& s, ProofCheck& C, const int32_t* target, uint64_t n_t
     return 0;
 }
 
+// 1b. (mi355sat_proof_deletions) The deletion lines resolved as include/mi355sat.h defines it: which lemma each one names,
+// hence per lemma the item it dies in front of and per item whether a group stands there; the counts and the peak of Live,
+// which are functions of the proof alone; the room for locked clauses.  Clauses compare as literal sets: sorted by
+// variable, repeats dropped.  Lemmas are found through a hash of that form - per hash the live lemma lines, latest last -
+// and compared literal by literal; the caller's clauses get their table only when a line finds no lemma.
+void proof_resolve_deletions(mi355sat& s, ProofCheck& C) {
+    const ProofLemmas& pf = C.pf;
+    mi355sat_proof_del_info& D = s.proof_del_info;
+    D = mi355sat_proof_del_info{};
+    s.proof_del_have = true;
+    C.del = true;
+    const uint64_t nl = pf.n_lemmas;
+    C.death.assign(C.n_items, UINT32_MAX);
+    C.group.assign(C.n_items, 0);
+    std::vector<int32_t> a, b;
+    auto canon = [](const int32_t* p, const int32_t* e, std::vector<int32_t>& out) {     // returns: x and ~x
+        out.assign(p, e);
+        std::sort(out.begin(), out.end(), [](int32_t x, int32_t y) { return std::abs(x) != std::abs(y) ? std::abs(x) < std::abs(y) : x < y; });
+        out.erase(std::unique(out.begin(), out.end()), out.end());
+        bool taut = false;
+        for (size_t i = 0; i + 1 < out.size(); i++) taut = taut || out[i] == -out[i + 1];
+        return taut;
+    };
+    auto hash = [](const std::vector<int32_t>& v) {
+        uint64_t h = 0xcbf29ce484222325ull;
+        for (int32_t x : v) h = (h ^ (uint32_t)x) * 0x100000001b3ull;
+        return h;
+    };
+    std::vector<uint32_t> words(nl, 0);           // per lemma: its room in the store
+    std::vector<uint8_t> joins(nl, 0);            // ... and whether it ever is in Live (a tautology is not)
+    std::unordered_map<uint64_t, std::vector<uint32_t>> live;
+    std::unordered_map<uint64_t, std::vector<uint64_t>> orig;
+    bool have_orig = false;
+    std::vector<uint32_t> dead_words;
+    uint64_t n_live = 0, w_live = 0, di = 0;
+    const uint64_t nd = pf.del_at.size();
+    for (uint64_t j = 0; j <= nl; j++) {
+        if (di < nd && pf.del_at[di] == j) D.groups++;
+        for (; di < nd && pf.del_at[di] == j; di++) {
+            canon(pf.del_lits.data() + pf.del_offs[di], pf.del_lits.data() + pf.del_offs[di + 1], a);
+            const uint64_t h = hash(a);
+            auto it = live.find(h);
+            bool found = false;
+            if (it != live.end())
+                for (size_t k = it->second.size(); k-- > 0 && !found;) {
+                    const uint32_t i = it->second[k];
+                    canon(pf.lits.data() + pf.offs[i], pf.lits.data() + pf.offs[i + 1], b);
+                    if (a != b) continue;
+                    found = true;
+                    it->second.erase(it->second.begin() + k);
+                    D.honoured++;
+                    if (!joins[i]) continue;          // a tautology: never attached
+                    C.death[i] = (uint32_t)j;
+                    C.group[j] = 1;
+                    n_live--;
+                    w_live -= words[i];
+                    dead_words.push_back(words[i]);
+                }
+            if (found) continue;
+            if (!have_orig) {
+                have_orig = true;
+                for (uint64_t c = 0; c + 1 < s.offs.size(); c++) {
+                    canon(s.lits.data() + s.offs[c], s.lits.data() + s.offs[c + 1], b);
+                    orig[hash(b)].push_back(c);
+                }
+            }
+            auto io = orig.find(h);
+            if (io != orig.end())
+                for (uint64_t c : io->second) {
+                    canon(s.lits.data() + s.offs[c], s.lits.data() + s.offs[c + 1], b);
+                    if (a == b) { found = true; break; }
+                }
+            if (found) D.ignored_original++;
+            else D.ignored_unmatched++;
+        }
+        if (j == nl) break;                           // the target never joins
+        const bool taut = canon(pf.lits.data() + pf.offs[j], pf.lits.data() + pf.offs[j + 1], a);
+        live[hash(a)].push_back((uint32_t)j);
+        if (taut) continue;
+        joins[j] = 1;
+        words[j] = (uint32_t)((a.size() + 3) & ~(size_t)3);
+        n_live++;
+        w_live += words[j];
+        D.peak_live_lemmas = std::max(D.peak_live_lemmas, n_live);
+        D.peak_live_words = std::max(D.peak_live_words, w_live);
+    }
+    // a worker keeps a dead lemma that is the reason of a level-0 fact: one per variable at most, the longest at worst
+    C.lock_slack = std::min<uint64_t>((uint64_t)s.max_var + 1, dead_words.size());
+    std::sort(dead_words.begin(), dead_words.end(), std::greater<uint32_t>());
+    for (uint64_t k = 0; k < C.lock_slack; k++) C.lock_slack_words += dead_words[k];
+    C.info.n_deletions_ignored = D.ignored_original + D.ignored_unmatched;
+}
+
 // 2. The answers that need no launch (an interrupt is consumed before the slabs are given up).  true: info.valid has one.
 bool proof_without_launch(mi355sat& s, ProofCheck& C) {
     if (s.interrupted.load()) {      // as a solve: an interrupt that came before the call stops it at once
@@ -3302,12 +3419,20 @@ void proof_device_form(ProofCheck& C) {
 
 // 4. The formula to the device with a learnt store that holds every lemma (each 16-byte aligned; add_learnt wants 8 words
 // of headroom), one worker per segment with its script - cursor, a, b, pad, checked (64 bit), attached (64 bit) - and
-// the proof behind it.
+// the proof behind it.  With deletion lines honoured the stores hold the peak of the live lemmas and the locked ones
+// (proof_resolve_deletions) instead of every lemma, the script has words [8] / [9] for the pass counters, and death[] goes
+// along.
 void proof_upload(mi355sat& s, ProofCheck& C, uint32_t segments) {
-    const uint32_t learnt_cap = (uint32_t)C.pf.n_lemmas + 1;
-    const uint32_t learnt_lit_cap = (uint32_t)(C.store_lits + 16);
+    mi355sat_proof_del_info& D = s.proof_del_info;
+    const uint32_t learnt_cap = C.del ? (uint32_t)std::max<uint64_t>(1, D.peak_live_lemmas + C.lock_slack) : (uint32_t)C.pf.n_lemmas + 1;
+    const uint32_t learnt_lit_cap = (uint32_t)((C.del ? D.peak_live_words + C.lock_slack_words : C.store_lits) + 16);
+    const uint32_t script_words = C.del ? 12 : 8;
     uint32_t S = std::min(segments ? segments : fleet_size(s), C.n_items);
-    upload_formula(s, C.P, 0, /*script_cap=*/8, S, 0, learnt_cap, learnt_lit_cap, MI355SAT_ERR_OOM);
+    upload_formula(s, C.P, 0, script_words, S, 0, learnt_cap, learnt_lit_cap, MI355SAT_ERR_OOM);
+    if (C.del) {
+        D.learnt_cap = s.L.learnt_cap; D.learnt_lit_cap = s.L.learnt_lit_cap; D.pool_cap = s.L.pool_cap;
+        C.d_death.upload(C.death, s.stream);
+    }
     S = std::min(S, s.n_workers);                // (what device memory holds)
     s.n_workers = s.n_alloc = S;
     C.S = C.info.segments = C.info.workers = S;
@@ -3316,13 +3441,16 @@ void proof_upload(mi355sat& s, ProofCheck& C, uint32_t segments) {
     for (uint32_t w = 0; w < S; w++) {
         const int32_t a = (int32_t)((uint64_t)C.n_items * w / S), b = (int32_t)((uint64_t)C.n_items * (w + 1) / S);
         script.insert(script.end(), {0, a, b, 0, 0, 0, 0, 0});
+        script.resize(script.size() + (script_words - 8), 0);
         soff.push_back(script.size());
     }
     reset_workers(s);
     customize(s, nullptr, nullptr, &script, &soff, S);
     C.d_lits.upload(C.dl, s.stream);
     C.d_offs.upload(C.doff, s.stream);
-    C.d_skip.upload(C.skip, s.stream);
+    std::vector<uint8_t> flags = C.skip;         // per item, bit 0: skip; bit 1 (the DEL builds): a group in front of it
+    if (C.del) for (uint32_t j = 0; j < C.n_items; j++) if (C.group[j]) flags[j] |= 2;
+    C.d_skip.upload(flags, s.stream);
     C.d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
 }
 
@@ -3352,13 +3480,15 @@ int proof_launches(mi355sat& s, ProofCheck& C, TrimRun* T) {
 int proof_verdict(mi355sat& s, ProofCheck& C) {
     mi355sat_proof_info& info = C.info;
     if (info.launches) {
-        std::vector<int32_t> sc((size_t)C.S * 8);
-        HIPCHK(hipMemcpy2D(sc.data(), 32, s.d_slabs.p + s.L.script, s.L.slab_bytes, 32, C.S, hipMemcpyDeviceToHost));
+        const size_t sw = C.del ? 12 : 8;
+        std::vector<int32_t> sc((size_t)C.S * sw);
+        HIPCHK(hipMemcpy2D(sc.data(), 4 * sw, s.d_slabs.p + s.L.script, s.L.slab_bytes, 4 * sw, C.S, hipMemcpyDeviceToHost));
         for (uint32_t w = 0; w < C.S; w++) {
             uint64_t c[2];
-            memcpy(c, &sc[(size_t)w * 8 + 4], sizeof c);
+            memcpy(c, &sc[(size_t)w * sw + 4], sizeof c);
             info.lemmas_checked += c[0];
             info.lemmas_attached += c[1];
+            if (C.del) { s.proof_del_info.skipped_locked += (uint32_t)sc[w * sw + 8]; s.proof_del_info.compactions += (uint32_t)sc[w * sw + 9]; }
         }
     }
     if (C.interrupted) {
@@ -3386,6 +3516,7 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
                      TrimRun* T) {
     ProofCheck C{pf, info};
     if (int rc = proof_target(s, C, target, n_target)) return rc;
+    if (s.proof_del) proof_resolve_deletions(s, C);
     if (!proof_without_launch(s, C)) {
         proof_device_form(C);
         proof_upload(s, C, segments);
@@ -3406,6 +3537,7 @@ int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_
     if (s->sweep) { s->err = std::string(name) + "() called during a sweep"; return MI355SAT_ERR_STATE; }
     if (!s->pending.empty()) { s->err = std::string(name) + "() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
     ProofLemmas pf;
+    pf.keep_deletions = s->proof_del;
     if (int rc = guarded(s, GUARD_HOST, [&] {
             std::vector<int32_t> text;
             if (!path) return parse_proof_words(*s, words, n_words, pf);
@@ -3704,6 +3836,19 @@ int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* targ
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch) {
     if (!s) return MI355SAT_ERR_ARG;
     s->proof_chunk = max_lemmas_per_launch;
+    return 0;
+}
+
+int mi355sat_proof_deletions(mi355sat* s, int on) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->proof_del = on != 0;
+    return 0;
+}
+
+int mi355sat_debug_proof_deletions(const mi355sat* s, mi355sat_proof_del_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    if (!s->proof_del_have) return MI355SAT_ERR_STATE;      // (const handle: no error text)
+    *out = s->proof_del_info;
     return 0;
 }
 

@@ -140,6 +140,15 @@ class Mi355SatTrimInfo(ctypes.Structure):   # mi355sat_trim_info
         return d
 
 
+class Mi355SatProofDelInfo(ctypes.Structure):   # mi355sat_proof_del_info
+    _fields_ = [(n, ctypes.c_uint64) for n in ("honoured", "ignored_original", "ignored_unmatched", "groups", "peak_live_lemmas",
+                                               "peak_live_words", "learnt_cap", "learnt_lit_cap", "pool_cap", "skipped_locked",
+                                               "compactions")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 TRIM_HINTS = 1   # MI355SAT_TRIM_HINTS
 
 
@@ -212,6 +221,8 @@ def _bind(L):
     L.mi355sat_check_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
     L.mi355sat_check_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
     L.mi355sat_debug_proof_check_chunk.argtypes = [vp, ctypes.c_uint32]
+    L.mi355sat_proof_deletions.argtypes = [vp, ctypes.c_int]
+    L.mi355sat_debug_proof_deletions.argtypes = [vp, ctypes.POINTER(Mi355SatProofDelInfo)]
     L.mi355sat_trim_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.POINTER(Mi355SatTrimInfo)]
     L.mi355sat_trim_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
@@ -370,7 +381,7 @@ class Mi355Sat:
 
     # ---- certificates: DRUP proofs checked on the device (include/mi355sat.h)
     def check_proof(self, proof, target=(), segments=0):
-        """Forward RUP check (deletion lines ignored) of `proof` - flat int32, lemmas 0-terminated, as dimacs.read_drup
+        """Forward RUP check (deletion lines ignored unless set_proof_deletions() is on) of `proof` - flat int32, lemmas 0-terminated, as dimacs.read_drup
         returns it - against this handle's clauses; `target` is the clause it must derive (default: the empty clause; for
         a solve under assumptions the negated core).  segments: into how many parts the lemma list is cut, one wavefront
         each (0 = the default); the verdict does not depend on it.  Returns mi355sat_proof_info as a dict: "valid" is the
@@ -394,6 +405,19 @@ class Mi355Sat:
     def debug_proof_check_chunk(self, max_lemmas_per_launch=0):
         """Test hook: at most this many lemmas per worker and launch of check_proof (0 = the default, time-bounded)."""
         self._check(self._L.mi355sat_debug_proof_check_chunk(self._h, int(max_lemmas_per_launch)), "debug_proof_check_chunk")
+
+    def set_proof_deletions(self, on=True):
+        """Honour the proof's deletion lines in check_proof / trim_proof and their _file forms (off by default: they are
+        counted and ignored).  A worker then holds only the live lemmas, its stores are sized from their peak, and a proof
+        that uses a lemma after deleting it is not valid.  The semantics: include/mi355sat.h, mi355sat_proof_deletions."""
+        self._check(self._L.mi355sat_proof_deletions(self._h, 1 if on else 0), "set_proof_deletions")
+
+    def debug_proof_deletions(self):
+        """mi355sat_proof_del_info of the last check or trim made with set_proof_deletions() on, as a dict (SolverError
+        ERR_STATE before the first one).  skipped_locked and compactions may differ from cut to cut and run to run."""
+        info = Mi355SatProofDelInfo()
+        self._check(self._L.mi355sat_debug_proof_deletions(self._h, ctypes.byref(info)), "debug_proof_deletions")
+        return info.as_dict()
 
     # ---- trimmed proofs: the clause core, the needed lemmas, LRAT (include/mi355sat.h)
     def _indices(self, fn, what):
