@@ -1688,6 +1688,81 @@ struct LoopState;
 #define MS_LBD_VIVIFIED 0x20000000u   // the clause went through vivify_pass once
 DEV void proof_log_deletions(Wk& w, const MsLayout& L, LoopState* pls, bool dl, uint32_t o0, uint32_t len);
 
+// ---- learnt store compaction ---------------------------------------------------------
+// rup_drop_dead's pass, shaped for reduce_db too - which keeps its own copy of the loop for now: as two callables its pass
+// costs the cold on_fixpoint four registers, and the full-fleet search builds then spill differently around that call.
+// The variable a clause locks - a watched literal that is TRUE with this clause as its reason - or -1 (one boolean and
+// a select: `>= 0` folds to reduce_db's test).
+template <bool LV>
+DEV int locked_var(const Wk& w, const MsShared& sh, const MsLayout& L, int w0, int w1, int cref) {
+    const bool by0 = lit_value<LV>(w, sh, L, w0) == MS_VAL_TRUE && VREC[w0 >> 1].reason == cref;
+    const bool locked = by0 || (lit_value<LV>(w, sh, L, w1) == MS_VAL_TRUE && VREC[w1 >> 1].reason == cref);
+    return locked ? (int)((uint32_t)(by0 ? w0 : w1) >> 1) : -1;
+}
+// One pass over the learnt store, 64 slots per chunk, one per lane.  keep(k, act, raw, rec, lockv) decides about slot k
+// (act: k is a slot; raw: its lc_lbd word) - all lanes call it in every chunk, before that chunk's literals move, so it
+// may hold ballots; false where !act.  Kept clauses move down in lc_lits and wl, in place; kept(k, nkk, start, raw, lockv)
+// gets each survivor's new slot and literal start: lc_lbd, remap and reasons are the caller's, who also owes the watch
+// lists a rebuild_watches if anything was dropped - the result.
+template <bool LV, class Keep, class Kept>
+DEV bool compact_learnts(Wk& w, const MsShared& sh, const MsLayout& L, Keep keep, Kept kept) {
+    Gp<MsClauseRec> lrec = WKA(MsClauseRec, wl) + sh.n_orig;   // records of the learnt clauses
+    Gp<const uint32_t> lc_lbd = WK_PTR(uint32_t, w, L, lc_lbd);
+    Gp<int32_t> lc_lits = WK_PTR(int32_t, w, L, lc_lits);
+    const uint32_t n = w.n_learnts;
+    uint32_t nk = 0, nlits = 0;
+    for (uint32_t k0 = 0; k0 < n; k0 += MS_WAVE) {
+        const uint32_t k = k0 + (uint32_t)w.lane;
+        const bool act = k < n;
+        uint32_t raw = 0;
+        MsClauseRec rec{0, 0, 0, 0};
+        int lockv = -1;
+        if (act) {
+            raw = lc_lbd[k];
+            rec = lrec[k];
+            lockv = locked_var<LV>(w, sh, L, rec.w0, rec.w1, (int)(sh.n_orig + k));
+        }
+        const bool kp = keep(k, act, raw, rec, lockv);
+        const u64 km = ballot(kp);
+        // exclusive prefix of (16-byte aligned) literal counts among kept clauses
+        const uint32_t len = kp ? rec.size : 0;
+        uint32_t pre = (len + 3u) & ~3u;
+        for (int o = 1; o < MS_WAVE; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)pre, o, 64);
+            if (w.lane >= o) pre += t;
+        }
+        const uint32_t total = (uint32_t)bcast((int)pre, 63);
+        pre -= (len + 3u) & ~3u;
+        const uint32_t nkk = nk + (uint32_t)popc64(km & lanemask_lt(w.lane));
+        wave_fence();
+        // move literals (dest <= source, clause by clause inside the chunk in lane order)
+        for (int src = 0; src < MS_WAVE; src++) {
+            if (!((km >> src) & 1)) continue;
+            const uint32_t so = (uint32_t)bcast((int)rec.start, src), slen = (uint32_t)bcast((int)len, src);
+            const uint32_t dd = nlits + (uint32_t)bcast((int)pre, src);
+            if (dd != so)
+                for (uint32_t t = 0; t < slen; t += MS_WAVE) {
+                    const uint32_t x = t + (uint32_t)w.lane;
+                    const int lv = x < slen ? lc_lits[so + x] : 0;
+                    wave_fence();
+                    if (x < slen) lc_lits[dd + x] = lv;
+                    wave_fence();
+                }
+        }
+        if (kp) {
+            lrec[nkk] = MsClauseRec{rec.w0, rec.w1, nlits + pre, len};
+            kept(k, nkk, nlits + pre, raw, lockv);
+        }
+        nk += (uint32_t)popc64(km);
+        nlits += total;
+        wave_fence();
+    }
+    w.n_learnts = nk;
+    w.lc_lits_n = nlits;
+    wave_fence();
+    return nk != n;
+}
+
 // ---- learnt clause database reduction ---------------------------------------
 // Keep every clause with lbd <= 2, every locked clause and every clause used
 // since the last reduction with lbd <= 6; of the rest drop the worse half by an
@@ -2836,24 +2911,34 @@ __global__ __launch_bounds__(MS_WAVE) void ms_core_model_kernel(MsLayout L, cons
     if (lane == 0) ((Gp<int32_t>)ok)[b] = bad ? 0 : 1;
 }
 
+// This lane's share of a round over the clause cl[.. e), 64 literals per round, one per lane, the round starting at k0:
+// in = the lane has a literal, ok = and it is in range.  lane_value: its value, `dflt` for a lane that is not ok.
+struct ClauseLane { bool in, ok; int lit; };
+DEV ClauseLane clause_lane(const Wk& w, const MsShared& sh, Gp<const int32_t> cl, uint32_t k0, uint32_t e) {
+    const uint32_t k = k0 + (uint32_t)w.lane;
+    const bool in = k < e;
+    const int lit = in ? cl[k] : 0;
+    return ClauseLane{in, in && (uint32_t)lit < 2u * sh.n_vars, lit};
+}
+template <bool LV>
+DEV int lane_value(const Wk& w, const MsShared& sh, const MsLayout& L, const ClauseLane& c, int dflt) {
+    return c.ok ? lit_value<LV>(w, sh, L, c.lit) : dflt;
+}
 // One clause under the level-0 assignment, for the kernels that attach clauses to a worker (ms_attach_kernel,
-// ms_rup_kernel): cl[b .. e), device literals, each variable at most once, 64 literals per round, one per lane.  sat: a
-// literal is TRUE; bad: one is out of range; else the free literals stand in learnt_buf[0 .. result), in clause order.
+// ms_rup_kernel): cl[b .. e), device literals, each variable at most once.  sat: a literal is TRUE; bad: one is out of
+// range; else the free literals stand in learnt_buf[0 .. result), in clause order.
 template <bool LV>
 DEV int attach_scan(const Wk& w, const MsShared& sh, const MsLayout& L, Gp<const int32_t> cl, uint32_t b, uint32_t e,
                     Gp<int32_t> learnt_buf, bool& sat, bool& bad) {
     sat = false; bad = false;
     int cnt = 0;
     for (uint32_t k0 = b; k0 < e && !sat && !bad; k0 += MS_WAVE) {
-        const uint32_t k = k0 + (uint32_t)w.lane;
-        const bool in = k < e;
-        const int lit = in ? cl[k] : 0;
-        const bool ok = (uint32_t)lit < 2u * sh.n_vars;
-        const int v = in && ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_FALSE;   // units attached before are visible
-        bad = ballot(in && !ok) != 0;
-        sat = ballot(in && v == MS_VAL_TRUE) != 0;
-        const u64 free_m = ballot(in && v == MS_VAL_UNDEF);
-        if ((free_m >> w.lane) & 1) learnt_buf[cnt + popc64(free_m & lanemask_lt(w.lane))] = lit;
+        const ClauseLane c = clause_lane(w, sh, cl, k0, e);
+        const int v = lane_value<LV>(w, sh, L, c, MS_VAL_FALSE);   // units attached before are visible
+        bad = ballot(c.in && !c.ok) != 0;
+        sat = ballot(v == MS_VAL_TRUE) != 0;
+        const u64 free_m = ballot(v == MS_VAL_UNDEF);
+        if ((free_m >> w.lane) & 1) learnt_buf[cnt + popc64(free_m & lanemask_lt(w.lane))] = c.lit;
         cnt += popc64(free_m);
     }
     wave_fence();
@@ -2942,17 +3027,14 @@ template <bool LV>
 DEV bool tr_lemma_marks(const Wk& w, const MsShared& sh, const MsLayout& L, Gp<const int32_t> cl, uint32_t b, uint32_t e, bool set) {
     bool any = false;
     for (uint32_t k0 = b; k0 < e; k0 += MS_WAVE) {
-        const uint32_t k = k0 + (uint32_t)w.lane;
-        const bool in = k < e;
-        const int lit = in ? cl[k] : 0;
-        const bool ok = in && (uint32_t)lit < 2u * sh.n_vars;
+        const ClauseLane c = clause_lane(w, sh, cl, k0, e);
         if (!set) {
-            if (ok) { tr_clr<LV>(w, L, lit >> 1, TR_ASSUMED); tr_clr<LV>(w, L, lit >> 1, TR_CAND); }
+            if (c.ok) { tr_clr<LV>(w, L, c.lit >> 1, TR_ASSUMED); tr_clr<LV>(w, L, c.lit >> 1, TR_CAND); }
             continue;
         }
-        const int v = ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_UNDEF;
-        if (v == MS_VAL_FALSE) tr_set<LV>(w, L, lit >> 1, TR_ASSUMED);
-        if (v == MS_VAL_TRUE) tr_set<LV>(w, L, lit >> 1, TR_CAND);
+        const int v = lane_value<LV>(w, sh, L, c, MS_VAL_UNDEF);
+        if (v == MS_VAL_FALSE) tr_set<LV>(w, L, c.lit >> 1, TR_ASSUMED);
+        if (v == MS_VAL_TRUE) tr_set<LV>(w, L, c.lit >> 1, TR_CAND);
         any = any || ballot(v != MS_VAL_UNDEF) != 0;
     }
     tr_sync<LV>();
@@ -3111,86 +3193,32 @@ DEV void rup_trace(Wk& w, const MsShared& sh, const MsLayout& L, const MsTrace& 
 }
 
 // ---- deletion lines honoured (mi355sat_proof_deletions, ms_rup_kernel<LV, TRACE, true>) ------
-// One pass over the learnt store in front of item j, reduce_db's shape with another rule: a slot whose lemma (the slab's
-// `remap` array: slot -> lemma) dies in front of an item <= j (death[lemma], written by the host from the resolved deletion
-// lines) goes, unless it is locked - a watched literal TRUE with this clause as its reason.  The trail holds level 0 only
-// and stands at its fixpoint, so a locked clause is satisfied for ever: keeping it changes no verdict, and rup_trace's
-// walk over the level-0 reasons stays valid.  It is counted once, at the item it dies in front of.  Kept clauses move down
-// in lc_lits / lc_lbd / wl with their remap entry; the reason and start of the variable a kept clause locks are repaired
-// as it moves (a new index is below every index still to be read, so no later lock test mistakes it); then the watch
-// lists are laid out again.  Nothing moves, and no list is rebuilt, when no slot dies.
+// compact_learnts in front of item j: a slot whose lemma (the slab's `remap` array: slot -> lemma) dies in front of an item
+// <= j (death[lemma], written by the host from the resolved deletion lines) goes, unless it is locked.  The trail holds
+// level 0 only and stands at its fixpoint, so a locked clause is satisfied for ever: keeping it changes no verdict, and
+// rup_trace's walk over the level-0 reasons stays valid.  It is counted once, at the item it dies in front of.  Unlike
+// reduce_db, which maps old slots to new ones and fixes the reasons in a pass over the trail, a kept clause here takes its
+// lc_lbd word and its remap entry along, and the reason and start of the variable it locks are repaired as it moves (a new
+// index is below every index still to be read, so no later lock test mistakes it).  No list is rebuilt when no slot dies.
 template <bool LV>
 DEV void rup_drop_dead(Wk& w, const MsShared& sh, const MsLayout& L, Gp<const uint32_t> death, uint32_t j, uint32_t& n_locked) {
-    Gp<MsClauseRec> lrec = WKA(MsClauseRec, wl) + sh.n_orig;
     Gp<uint32_t> lc_lbd = WK_PTR(uint32_t, w, L, lc_lbd);
-    Gp<int32_t> lc_lits = WK_PTR(int32_t, w, L, lc_lits);
     Gp<uint32_t> slot_lemma = WK_PTR(uint32_t, w, L, remap);
-    const uint32_t n = w.n_learnts;
-    uint32_t nk = 0, nlits = 0;
-    for (uint32_t k0 = 0; k0 < n; k0 += MS_WAVE) {
-        const uint32_t k = k0 + (uint32_t)w.lane;
-        const bool act = k < n;
-        bool dead = false, late = false;
-        uint32_t o0 = 0, len = 0, raw = 0, jl = 0;
-        int2 ww = make_int2(0, 0);
-        int lockv = -1;                 // the variable this clause is the reason of
-        if (act) {
-            raw = lc_lbd[k];
-            jl = slot_lemma[k];
-            const MsClauseRec ch = lrec[k];
-            o0 = ch.start;
-            len = ch.size;
-            ww = make_int2(ch.w0, ch.w1);
-            const int cref = (int)(sh.n_orig + k);
-            if (lit_value<LV>(w, sh, L, ww.x) == MS_VAL_TRUE && VREC[ww.x >> 1].reason == cref) lockv = ww.x >> 1;
-            else if (lit_value<LV>(w, sh, L, ww.y) == MS_VAL_TRUE && VREC[ww.y >> 1].reason == cref) lockv = ww.y >> 1;
-            const uint32_t d = death[jl];
-            dead = d <= j;
-            late = d == j;
-        }
-        n_locked += (uint32_t)popc64(ballot(late && lockv >= 0));
-        const bool keep = act && (!dead || lockv >= 0);
-        const u64 km = ballot(keep);
-        if (!keep) len = 0;
-        // exclusive prefix of (16-byte aligned) literal counts among kept clauses
-        uint32_t pre = (len + 3u) & ~3u;
-        for (int o = 1; o < MS_WAVE; o <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)pre, o, 64);
-            if (w.lane >= o) pre += t;
-        }
-        const uint32_t total = (uint32_t)bcast((int)pre, 63);
-        pre -= (len + 3u) & ~3u;
-        const uint32_t nkk = nk + (uint32_t)popc64(km & lanemask_lt(w.lane));
-        wave_fence();
-        // move literals (dest <= source, clause by clause inside the chunk in lane order)
-        for (int src = 0; src < MS_WAVE; src++) {
-            if (!((km >> src) & 1)) continue;
-            const uint32_t so = (uint32_t)bcast((int)o0, src), slen = (uint32_t)bcast((int)len, src);
-            const uint32_t dd = nlits + (uint32_t)bcast((int)pre, src);
-            if (dd != so)
-                for (uint32_t t = 0; t < slen; t += MS_WAVE) {
-                    const uint32_t x = t + (uint32_t)w.lane;
-                    const int lv = x < slen ? lc_lits[so + x] : 0;
-                    wave_fence();
-                    if (x < slen) lc_lits[dd + x] = lv;
-                    wave_fence();
-                }
-        }
-        if (keep) {
-            lrec[nkk] = MsClauseRec{ww.x, ww.y, nlits + pre, len};
+    uint32_t jl = 0;                    // the lemma this lane's slot of the chunk holds
+    const bool dropped = compact_learnts<LV>(
+        w, sh, L,
+        [&](uint32_t k, bool act, uint32_t, const MsClauseRec&, int lockv) {
+            jl = act ? slot_lemma[k] : 0;
+            const uint32_t d = act ? death[jl] : 0xffffffffu;
+            n_locked += (uint32_t)popc64(ballot(d == j && lockv >= 0));
+            return act && (d > j || lockv >= 0);
+        },
+        [&](uint32_t, uint32_t nkk, uint32_t start, uint32_t raw, int lockv) {
             lc_lbd[nkk] = raw;
             slot_lemma[nkk] = jl;
-            if (lockv >= 0) { VREC[lockv].reason = (int)(sh.n_orig + nkk); VREC[lockv].start = nlits + pre; }
-        }
-        nk += (uint32_t)popc64(km);
-        nlits += total;
-        wave_fence();
-    }
-    if (nk == n) return;
-    w.n_learnts = nk;
-    w.lc_lits_n = nlits;
-    wave_fence();
-    rebuild_watches(w, sh, L);
+            if (lockv >= 0) { VREC[lockv].reason = (int)(sh.n_orig + nkk); VREC[lockv].start = start; }
+        });
+    if (dropped) rebuild_watches(w, sh, L);
 }
 
 // ---- forward RUP check of a clausal proof (mi355sat_check_proof) -------------------------
@@ -3312,17 +3340,14 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             new_decision_level<LV>(w, sh, L);
             bool rup = false, bad = false;
             for (uint32_t k0 = lb; k0 < le && !rup && !bad; k0 += MS_WAVE) {
-                const uint32_t k = k0 + (uint32_t)w.lane;
-                const bool in = k < le;
-                const int lit = in ? cl[k] : 0;
-                const bool ok = (uint32_t)lit < 2u * sh.n_vars;
-                const int v = in && ok ? lit_value<LV>(w, sh, L, lit) : MS_VAL_FALSE;
-                bad = ballot(in && !ok) != 0;
-                rup = ballot(in && v == MS_VAL_TRUE) != 0;
+                const ClauseLane c = clause_lane(w, sh, cl, k0, le);
+                const int v = lane_value<LV>(w, sh, L, c, MS_VAL_FALSE);
+                bad = ballot(c.in && !c.ok) != 0;
+                rup = ballot(v == MS_VAL_TRUE) != 0;
                 if (bad || rup) break;
                 // (each variable at most once per lemma: the negations neither repeat nor clash)
                 wave_fence();
-                assign_winners<LV>(w, sh, L, in && v == MS_VAL_UNDEF, lit ^ 1, MS_REASON_NONE);
+                assign_winners<LV>(w, sh, L, v == MS_VAL_UNDEF, c.lit ^ 1, MS_REASON_NONE);
                 lds_fence();
             }
             if (bad) { w.status = MS_ST_ERR_INTERNAL; break; }
