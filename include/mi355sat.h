@@ -696,6 +696,80 @@ int mi355sat_trim_write_lrat(mi355sat* s, const char* path);   /* MI355SAT_ERR_S
  * the largest size (8 * (n_vars + 3) words): a worker ends its launch when less than that is free. */
 int mi355sat_debug_trim_log(mi355sat* s, uint32_t words_per_worker);
 
+/* Check an LRAT file on the device: the certificate at the end of the chain (ms_lrat_kernel).  What
+ * mi355sat_trim_write_lrat writes is verified here by a kernel that shares nothing with the propagation code whose answer
+ * it certifies - and by any LRAT checker a third party brings.
+ * Semantics: strict, exactly those of tests/lrat_check.py.  Trusted base: the handle's clauses as the caller added them;
+ * clause i, 0-based in add order, has id i + 1; no simplification, the caller's variables; new, add_cnf, check_lrat is a
+ * valid sequence.  A line is `id literals 0 hints 0`.  It is accepted when, under the negation of its literals, the hinted
+ * clauses are, in the order given, unit one after the other, and the last one is falsified.  Free literals count as a
+ * set (a clause that repeats its one free literal is unit); a hinted clause that holds x and -x is satisfied if x is
+ * assigned and has two free literals if not.  The smallest rejected line index is the file's verdict; within a line the
+ * reasons have this precedence: */
+#define MI355SAT_LRAT_ID_ORDER 1               /* id not above the originals' / not increasing */
+#define MI355SAT_LRAT_TAUTOLOGY 2              /* the line's clause holds a literal and its negation */
+#define MI355SAT_LRAT_NO_HINTS 3
+#define MI355SAT_LRAT_BAD_HINT 4               /* at its turn: the hint is neither an original nor an earlier line */
+#define MI355SAT_LRAT_HINT_SATISFIED 5         /* at its turn: the hinted clause has a true literal (free ones or not) */
+#define MI355SAT_LRAT_HINT_NOT_UNIT 6          /* two or more DISTINCT free literals */
+#define MI355SAT_LRAT_HINT_FALSIFIED_EARLY 7   /* falsified before the last hint */
+#define MI355SAT_LRAT_LAST_NOT_FALSIFIED 8     /* the last hint leaves a free literal */
+/* target as in mi355sat_check_proof (n_target = 0: the empty clause): derives_target = 1 iff the last line's literals
+ * equal the target as a set; a tautological target is derived by any file (the trimmer writes no line for one).
+ * valid = accepted && derives_target.
+ * lines: flat int32, `id, literals, 0, hints, 0` per line.  Input that is not LRAT at all is MI355SAT_ERR_ARG, found on the
+ * host before anything is uploaded or launched, with the text in mi355sat_last_error: a line that is not integers, a
+ * missing terminator, a deletion line (`id d ...`), a zero or negative hint or id, a literal whose variable is above the
+ * handle's highest (mi355sat_reserve raises that).
+ * How: the caller's clauses and the lines are one read-only database; every hint id is rewritten on the host to a clause
+ * index of it (an id that names nothing earlier: a sentinel the device reports at the hint's turn).  One wavefront per
+ * line, workgroups of one wavefront, the lines of a launch strided over at most 4096 of them; lines go in file order in
+ * launches of 2^24 hints (about 20 ms at the measured 7e8 hints a second), the interrupt is polled between launches, and the
+ * first launch with a rejection ends the call.
+ * The wave's assignment map is 2 bits per variable in LDS, cleared per line, when opts.lds_val forces it (up to 64 KB) or, on
+ * auto, when it takes at most 9.4 KB (16 workgroups per CU in the 150 KB the search builds budget); else one stamped word per
+ * variable and wave in HBM that is never cleared.  A hostile file can produce a rejection and nothing else: after the
+ * host's validation no index the kernel uses comes unvalidated from the file, and the kernel itself refuses a hint that is
+ * not below the line's own index.
+ * Returns 0 when the check ran to its end; MI355SAT_INTERRUPTED (0 as well) with accepted = -1 when interrupted: the call
+ * consumes the interrupt, and one that arrived before the call stops it before the first launch (also a call whose file
+ * needs no launch).  A call refused with an error still writes *out (nothing accepted, nothing rejected) once its
+ * arguments are not NULL, and ends the result mi355sat_lrat_used held.  During a
+ * mi355sat_sweep_*: MI355SAT_ERR_STATE.  The call owns its device buffers and does not touch the worker slabs: assumptions,
+ * failed / core, the phase hints, a trim result on the handle (trim, check_lrat_file, trim_core in sequence works) and what
+ * is resident for a warm incremental solve all stay - the next solve() still starts warm.  n_sat / n_unsat / n_terminated
+ * do not count the call; solve_seconds, kernel_seconds and kernel_launches accumulate.
+ * Measured (MI355X, profiles/r11_lrat_check.log: scripts/gpu_lrat_check.py, beside tests/lrat_check.py on the same file, three
+ * runs each way, alternating).  rect 16x16 k = 3, the fleet's trimmed proof (144 lines, 25 873 hints, 163 KB):
+ * 0.001-0.002 s, kernel 0.9 ms, beside 0.016-0.018 s in Python.  rect 24x24 k = 8 (30 845 lines, 7 558 306 hints, clauses of up
+ * to 466 literals, 52.9 MB): 0.16-0.17 s for the call - kernel 10.3 ms on 4096 waves, 0.028 s behind the parser, the rest the
+ * host reading 53 MB of text - beside 5.0-5.1 s in Python and 7.0 s for the trim that produced the file.  Another solve of
+ * that bound (42 296 lines, 9 789 662 hints, 71.0 MB): 0.18 s, kernel 8.9 ms in one launch, Python 6.1-6.3 s, trim 13.2 s;
+ * with the map in HBM (lds_val = -1) the same 0.18 s and 8.7-8.8 ms. */
+typedef struct mi355sat_lrat_info {
+    int32_t  valid, accepted;        /* accepted: 1 every line accepted, 0 one rejected, -1 interrupted */
+    int32_t  derives_target, reason; /* reason: MI355SAT_LRAT_* of the first rejected line, 0 if none */
+    uint64_t n_lines, n_hints;       /* of the file */
+    uint64_t first_rejected;         /* line index, 0-based; UINT64_MAX if none */
+    uint64_t first_rejected_id;      /* its id as written */
+    uint64_t reject_hint;            /* position of the offending hint in that line (reasons 4..8), else UINT64_MAX */
+    uint64_t used_originals;         /* distinct caller clauses hinted (0 unless accepted == 1) */
+    uint64_t longest_clause;         /* literals, over the caller's clauses and the lines uploaded */
+    int32_t  lds;  uint32_t dyn_lds_bytes;   /* which build ran, as mi355sat_search_build reports it */
+    uint64_t waves, launches;        /* wavefronts of the largest launch; launches */
+    double   seconds, kernel_seconds;
+} mi355sat_lrat_info;
+int mi355sat_check_lrat(mi355sat* s, const int32_t* lines, uint64_t n_words, const int32_t* target, uint64_t n_target,
+                        mi355sat_lrat_info* out);
+/* The same for an LRAT text file, one line per clause, as mi355sat_trim_write_lrat writes it. */
+int mi355sat_check_lrat_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, mi355sat_lrat_info* out);
+/* After a check that accepted every line (accepted == 1), until the next check or a clause added: the caller clauses some
+ * line hinted, 0-based indices, ascending.  out NULL sizes (*n), a cap too small is MI355SAT_ERR_ARG, any other state
+ * MI355SAT_ERR_STATE - as mi355sat_trim_core. */
+int mi355sat_lrat_used(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n);
+/* Test hook: at most this many lines per launch; 0 = the default (launches of about 20 ms: 2^24 hints). */
+int mi355sat_debug_lrat_chunk(mi355sat* s, uint32_t max_lines_per_launch);
+
 #ifdef __cplusplus
 }
 #endif

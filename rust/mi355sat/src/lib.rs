@@ -77,6 +77,27 @@ pub struct TrimInfo {
 /// `MI355SAT_TRIM_HINTS`: keep what `write_lrat` needs.
 pub const TRIM_HINTS: u32 = 1;
 
+/// Mirror of `mi355sat_lrat_info`: what `check_lrat_file` found.
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct LratInfo {
+    /// `accepted && derives_target`
+    pub valid: i32,
+    /// 1: every line accepted; 0: one rejected; -1: the check was interrupted
+    pub accepted: i32,
+    pub derives_target: i32,
+    /// `MI355SAT_LRAT_*` of the first rejected line (1 id order .. 8 last hint not falsified), 0 if none
+    pub reason: i32,
+    pub n_lines: u64, pub n_hints: u64,
+    /// 0-based index of the first rejected line and its id as written; `u64::MAX` if none
+    pub first_rejected: u64, pub first_rejected_id: u64,
+    /// position of the offending hint in that line (reasons 4..8), else `u64::MAX`
+    pub reject_hint: u64,
+    pub used_originals: u64, pub longest_clause: u64,
+    pub lds: i32, pub dyn_lds_bytes: u32,
+    pub waves: u64, pub launches: u64, pub seconds: f64, pub kernel_seconds: f64,
+}
+
 extern "C" {
     fn mi355sat_new(opts: *const Opts) -> *mut c_void;
     fn mi355sat_free(s: *mut c_void);
@@ -98,6 +119,8 @@ extern "C" {
     fn mi355sat_trim_core(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_trim_lemmas(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_trim_write_lrat(s: *mut c_void, path: *const c_char) -> c_int;
+    fn mi355sat_check_lrat_file(s: *mut c_void, path: *const c_char, target: *const i32, n_target: u64, out: *mut LratInfo) -> c_int;
+    fn mi355sat_lrat_used(s: *mut c_void, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
     fn mi355sat_interrupt(s: *mut c_void);
     fn mi355sat_stats(s: *const c_void, out: *mut Stats) -> c_int;
     fn mi355sat_set_incremental(s: *mut c_void, on: c_int) -> c_int;
@@ -217,6 +240,20 @@ impl Mi355Sat {
         if unsafe { mi355sat_trim_write_lrat(self.h, p.as_ptr()) } < 0 { return Err(self.err()); }
         Ok(())
     }
+    /// Strict LRAT check on the device (`mi355sat_check_lrat_file`) of a file as `write_lrat` writes it, against this
+    /// handle's clauses (clause i, 0-based in add order, has id i + 1): `valid == 1` iff every line is accepted and the
+    /// last one is `target` (empty: the empty clause).  The kernel shares nothing with the solver's propagation; the call
+    /// leaves the handle's solve state, cores and trim result alone.  Input that is not LRAT at all is an error.
+    pub fn check_lrat_file(&mut self, path: &std::path::Path, target: &[i32]) -> anyhow::Result<LratInfo> {
+        let p = std::ffi::CString::new(path.to_string_lossy().as_bytes())?;
+        let mut info = LratInfo::default();
+        let rc = unsafe { mi355sat_check_lrat_file(self.h, p.as_ptr(), target.as_ptr(), target.len() as u64, &mut info) };
+        if rc < 0 { return Err(self.err()); }
+        Ok(info)
+    }
+    /// After a `check_lrat_file` that accepted every line: the clauses of this handle some line hinted, ascending; an
+    /// error (`MI355SAT_ERR_STATE`) in any other state.
+    pub fn lrat_used(&mut self) -> anyhow::Result<Vec<u64>> { self.indices(mi355sat_lrat_used) }
     fn err(&self) -> anyhow::Error {
         let m = unsafe { std::ffi::CStr::from_ptr(mi355sat_last_error(self.h)) };
         anyhow::anyhow!(m.to_string_lossy().into_owned())

@@ -4,8 +4,8 @@ from .encoder import (PLATFORMS_DEFAULT, Cnf, Encoding, EncoderError, PlatformLa
                       ValidationResult, WorldGrid)
 from .loop import (run_solver, solver_loop, solver_loop_fan, solver_loop_incremental, solver_loop_pair, solver_loop_sweep,
                    weight_loop)
-from .solver import ColdReason, Mi355Sat, SolverError, SolverResult, algorithmic_bytes
+from .solver import ColdReason, LratReason, Mi355Sat, SolverError, SolverResult, algorithmic_bytes
 
 __all__ = ["PLATFORMS_DEFAULT", "Cnf", "Encoding", "EncoderError", "PlatformLayout", "PlatformLimits",
-           "ValidationResult", "WorldGrid", "run_solver", "solver_loop", "solver_loop_fan", "solver_loop_incremental", "solver_loop_pair", "solver_loop_sweep", "weight_loop", "ColdReason", "Mi355Sat", "SolverError",
+           "ValidationResult", "WorldGrid", "run_solver", "solver_loop", "solver_loop_fan", "solver_loop_incremental", "solver_loop_pair", "solver_loop_sweep", "weight_loop", "ColdReason", "LratReason", "Mi355Sat", "SolverError",
            "SolverResult", "algorithmic_bytes"]

@@ -3410,3 +3410,133 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
     }
     wk_store<LV>(w, sh, L, __builtin_readcyclecounter() - t0);
 }
+
+// ---- strict LRAT check (mi355sat_check_lrat) --------------------------------------------
+// A certificate checker shares nothing with the propagation code whose answer it certifies: this section uses the wave
+// primitives at the top of the file (ballot, bcast, uni, the fences, lds_or) and nothing of BCP, watches or analysis.
+// The database is one read-only CSR: the caller's clauses (indices 0 .. n_orig - 1) and behind them the file's lines in file
+// order (line i = clause n_orig + i), device literals 2 * var + sign in the caller's variables.  The host has validated the
+// file and rewritten every hint id to such a clause index, MS_LRAT_NONE for an id that names nothing below the line's own;
+// the kernel still refuses any hint that is not below the line's own index, so no index it uses comes unvalidated from the
+// file.  A line is accepted when, under the negation of its literals, the hinted clauses are unit one after the other, in
+// the order given, and the last one is falsified (tests/lrat_check.py is the specification, precedence of the reasons
+// included).  Lines do not depend on each other: a workgroup is one wavefront and takes the lines of the launch strided by
+// the grid; within a line there is one chain of dependent clause reads.
+//   per line: the negated literals go into the wave's assignment map, 64 per step - each lane looks first (its literal TRUE
+//             already: the clause holds it and its negation), writes, and reads back (two lanes of one step wrote x and ~x:
+//             one of them lost); then hint by hint the clause's offset pair and its literals, 64 per step: a TRUE literal
+//             rejects whatever else the clause holds, the free lanes compare their literal with the first free one, which is
+//             carried from step to step so that "two DISTINCT free literals" holds over the whole clause; the unit is
+//             applied, the last hint judged.
+//   LV:       the map is 2 bits per variable in dynamic LDS (bit 1 assigned, bit 0 the sign of the TRUE literal), cleared
+//             per line;
+//   else:     one word per variable per wave in HBM, never cleared: (stamp << 2 | the two bits), stamp = the line's number
+//             + 1, which a wave meets in increasing order - a value counts iff its stamp is the current line's.
+// Results: rec[4 * wave] = {line, reason, hint position, -} of the FIRST line the wave rejects (it stops there: its later
+// lines are behind that one), all ones while it has none; the host takes the minimum over the waves.  used: one bit per
+// caller clause that a hint named at its turn, set by one lane.
+#define MS_LRAT_NONE 0xffffffffu
+enum { MS_LRAT_ID_ORDER = 1, MS_LRAT_TAUTOLOGY, MS_LRAT_NO_HINTS, MS_LRAT_BAD_HINT, MS_LRAT_HINT_SATISFIED, MS_LRAT_HINT_NOT_UNIT,
+       MS_LRAT_HINT_FALSIFIED_EARLY, MS_LRAT_LAST_NOT_FALSIFIED };
+struct MsLrat {
+    const int32_t* lits;
+    const uint32_t* offs;       // n_orig + n_lines + 1
+    const uint32_t* hints;      // clause indices, MS_LRAT_NONE: names nothing
+    const uint32_t* hoffs;      // n_lines + 1
+    uint32_t* used;             // (n_orig + 31) / 32 words
+    uint32_t* rec;              // 4 words per wave
+    uint32_t* map;              // (not LV) n_vars words per wave
+    uint32_t n_orig, n_vars, line0, line1;   // this launch checks lines [line0, line1)
+};
+
+template <bool LV>
+DEV int lrat_value(LdsU32 lmap, Gp<uint32_t> gmap, uint32_t stamp, int lit) {
+    const int v = lit >> 1;
+    uint32_t x;
+    if (LV) x = (lmap[v >> 4] >> ((v & 15) * 2)) & 3u;
+    else {
+        const uint32_t wv = gmap[v];
+        x = (wv >> 2) == stamp ? (wv & 3u) : 0u;
+    }
+    return (x & 2u) ? (int)((x ^ (uint32_t)lit) & 1u) : MS_VAL_UNDEF;
+}
+template <bool LV>
+DEV void lrat_set_true(LdsU32 lmap, Gp<uint32_t> gmap, uint32_t stamp, int lit) {
+    const int v = lit >> 1;
+    if (LV) lds_or(&lmap[v >> 4], (2u | (uint32_t)(lit & 1)) << ((v & 15) * 2));
+    else gmap[v] = (stamp << 2) | 2u | (uint32_t)(lit & 1);
+}
+
+template <bool LV>
+__global__ __launch_bounds__(MS_WAVE) void ms_lrat_kernel(MsLrat A) {
+    HIP_DYNAMIC_SHARED(uint32_t, s_lmap)
+    const int lane = (int)threadIdx.x;
+    const uint32_t wave = blockIdx.x;
+    LdsU32 lmap = (LdsU32)s_lmap;
+    Gp<uint32_t> gmap = LV ? (Gp<uint32_t>) nullptr : (Gp<uint32_t>)A.map + (size_t)wave * A.n_vars;
+    Gp<const int32_t> cl = (Gp<const int32_t>)A.lits;
+    Gp<const uint32_t> co = (Gp<const uint32_t>)A.offs;
+    Gp<const uint32_t> hl = (Gp<const uint32_t>)A.hints;
+    Gp<const uint32_t> ho = (Gp<const uint32_t>)A.hoffs;
+    const uint32_t map_words = (A.n_vars + 15) >> 4;
+    for (uint32_t line = A.line0 + wave; line < A.line1; line += gridDim.x) {
+        const uint32_t own = A.n_orig + line, stamp = line + 1;
+        uint32_t reason = 0, at = MS_LRAT_NONE;
+        if (LV) {
+            for (uint32_t i = (uint32_t)lane; i < map_words; i += MS_WAVE) lmap[i] = 0;
+            lds_fence();
+        }
+        // the negation of the line's clause
+        const uint32_t lb = (uint32_t)uni((int)co[own]), le = (uint32_t)uni((int)co[own + 1]);
+        for (uint32_t k0 = lb; k0 < le && !reason; k0 += MS_WAVE) {
+            const bool in = k0 + (uint32_t)lane < le;
+            const int lit = in ? cl[k0 + (uint32_t)lane] : 0;
+            bool taut = ballot(in && lrat_value<LV>(lmap, gmap, stamp, lit) == MS_VAL_TRUE) != 0;       // ~lit came in an earlier step
+            if (!taut) {
+                if (in) lrat_set_true<LV>(lmap, gmap, stamp, lit ^ 1);
+                if (LV) lds_fence(); else wave_fence();
+                taut = ballot(in && lrat_value<LV>(lmap, gmap, stamp, lit) != MS_VAL_FALSE) != 0;       // ... or in this one
+            }
+            if (taut) reason = MS_LRAT_TAUTOLOGY;
+        }
+        const uint32_t hb = (uint32_t)uni((int)ho[line]), he = (uint32_t)uni((int)ho[line + 1]);
+        if (!reason && he == hb) reason = MS_LRAT_NO_HINTS;
+        for (uint32_t k = hb; k < he && !reason; k++) {
+            const uint32_t h = (uint32_t)uni((int)hl[k]);
+            at = k - hb;
+            if (h >= own) { reason = MS_LRAT_BAD_HINT; break; }
+            const uint32_t cb = (uint32_t)uni((int)co[h]), ce = (uint32_t)uni((int)co[h + 1]);
+            bool sat = false, two = false, have = false;
+            int free_lit = 0;
+            for (uint32_t c0 = cb; c0 < ce; c0 += MS_WAVE) {
+                const bool in = c0 + (uint32_t)lane < ce;
+                const int lit = in ? cl[c0 + (uint32_t)lane] : 0;
+                const int v = in ? lrat_value<LV>(lmap, gmap, stamp, lit) : MS_VAL_FALSE;
+                if (ballot(v == MS_VAL_TRUE) != 0) { sat = true; break; }
+                const u64 fm = ballot(v == MS_VAL_UNDEF);
+                if (fm == 0) continue;
+                if (!have) { free_lit = bcast(lit, first_lane(fm)); have = true; }
+                if (ballot(v == MS_VAL_UNDEF && lit != free_lit) != 0) two = true;     // (a TRUE literal further on still wins)
+            }
+            const bool last = k + 1 == he;
+            if (sat) reason = MS_LRAT_HINT_SATISFIED;
+            else if (two) reason = MS_LRAT_HINT_NOT_UNIT;
+            else if (!have && !last) reason = MS_LRAT_HINT_FALSIFIED_EARLY;
+            else if (have && last) reason = MS_LRAT_LAST_NOT_FALSIFIED;
+            if (reason) break;
+            if (h < A.n_orig && lane == 0) (void)atomicOr(&A.used[h >> 5], 1u << (h & 31));
+            if (have) {
+                if (lane == 0) lrat_set_true<LV>(lmap, gmap, stamp, free_lit);
+                if (LV) lds_fence(); else wave_fence();
+            }
+        }
+        if (reason) {
+            if (reason < MS_LRAT_BAD_HINT) at = MS_LRAT_NONE;
+            if (lane == 0) {
+                Gp<uint32_t> r = (Gp<uint32_t>)A.rec + 4 * (size_t)wave;
+                r[0] = line; r[1] = reason; r[2] = at; r[3] = 0;
+            }
+            break;
+        }
+    }
+}

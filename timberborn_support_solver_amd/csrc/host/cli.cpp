@@ -1,5 +1,5 @@
 // tbs_cli — minimal command-line driver of the solve path (NOT the reference's REPL/UI):
-//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions]]
+//   tbs_cli rect W H [-l1:K] [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] [--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions] [--verify]]
 //   tbs_cli file PATH.toml [-l1:K] ...
 // Mirrors `solve -l<dims>:<n>` of crates/repl/src/main.rs:44-75,248-261: encode once, then solver_loop.
 // Ctrl-C calls mi355sat_interrupt (main.rs:297-324).
@@ -7,6 +7,8 @@
 // PATH, the proof is checked and trimmed on a fresh handle (mi355sat_trim_proof_file) and PATH.lrat is written: a certificate
 // that a checker of a few dozen lines verifies against the bound's CNF.  --honour-deletions: the check honours the proof's
 // deletion lines (mi355sat_proof_deletions): a worker's stores hold the live lemmas only; the output gains one line.
+// --verify: PATH.lrat is then checked on another fresh handle that holds the bound's CNF (mi355sat_check_lrat_file, a kernel
+// that shares nothing with the solver's propagation); one more line, `Verified: ...`, and a rejection exits non-zero.
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +20,7 @@
 static std::atomic<mi355sat*> g_current{nullptr};
 static std::atomic<int> g_interrupted{0};
 // The UNSAT bound once more with a proof, trimmed on a fresh handle.  Returns false if the answer was not UNSAT again.
-static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::string& path, bool honour_deletions) {
+static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::string& path, bool honour_deletions, bool verify) {
     auto fail = [](mi355sat* s, const char* ctx) {
         const std::string m = std::string(ctx) + ": " + mi355sat_last_error(s);
         mi355sat_free(s);
@@ -60,6 +62,26 @@ static bool certify(const tbs::Cnf& cnf, const mi355sat_opts& opts, const std::s
     std::cout << "Certificate: " << lrat << " - core " << info.core_clauses << " of " << cnf.n_clauses() << " clauses, "
               << info.lemmas_needed << " of " << info.check.n_lemmas << " lemmas needed (checked in " << info.check.seconds
               << " s)" << std::endl;
+    if (!verify) return true;
+    s = mi355sat_new(&opts);
+    if (!s) throw std::runtime_error(std::string("Failed to create solver: ") + mi355sat_last_error(nullptr));
+    if (mi355sat_add_cnf(s, cnf.lits.data(), cnf.offsets.data(), cnf.n_clauses()) < 0) fail(s, "Failed to add CNF");
+    mi355sat_reserve(s, cnf.n_vars);
+    mi355sat_lrat_info li{};
+    g_current.store(s);
+    const int lr = mi355sat_check_lrat_file(s, lrat.c_str(), nullptr, 0, &li);
+    g_current.store(nullptr);
+    if (lr < 0) fail(s, "check_lrat");
+    mi355sat_free(s);
+    if (li.valid != 1) {
+        // (`Verified:` begins the line of a success only)
+        if (li.accepted < 0) std::cout << "Verification interrupted" << std::endl;
+        else if (li.accepted == 1) std::cout << "Verification failed: " << lrat << " does NOT derive the empty clause" << std::endl;
+        else std::cout << "Verification failed: " << lrat << " was NOT accepted - line " << li.first_rejected << " (id " << li.first_rejected_id
+                       << "), reason " << li.reason << std::endl;
+        return false;
+    }
+    std::cout << "Verified: " << lrat << " - " << li.n_lines << " lines, " << li.n_hints << " hints, " << li.seconds << " s" << std::endl;
     return true;
 }
 
@@ -74,7 +96,7 @@ int main(int argc, char** argv) {
     try {
         if (argc < 3) {
             fprintf(stderr, "usage: %s rect W H | file PATH [-l<dims>:<n>]... [--platforms default|1x1] [--workers N] [--sweep | --incremental | --phase-hints] [--gpu N] [--seed N] "
-                            "[--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions]]\n", argv[0]);
+                            "[--verbose] [--no-simp] [--eliminate] [--certify PATH [--honour-deletions] [--verify]]\n", argv[0]);
             return 2;
         }
         WorldGrid grid;
@@ -88,7 +110,7 @@ int main(int argc, char** argv) {
         opts.device = -1;
         bool sweep = false, incremental = false, phase_hints = false;
         std::string certify_path;
-        bool honour_deletions = false;
+        bool honour_deletions = false, verify = false;
         for (; a < argc; a++) {
             std::string arg = argv[a];
             if (arg.rfind("-l", 0) == 0) {             // -l<dims>:<n>, dims = AxB or A (=AxA), main.rs:120-142
@@ -113,6 +135,7 @@ int main(int argc, char** argv) {
             else if (arg == "--phase-hints") phase_hints = true;   // every rung starts its search at the layout of the rung before (mi355sat_set_phases)
             else if (arg == "--certify" && a + 1 < argc) certify_path = argv[++a];
             else if (arg == "--honour-deletions") honour_deletions = true;
+            else if (arg == "--verify") verify = true;
             else throw std::runtime_error("unknown argument " + arg);
         }
         Encoding enc = Encoding::encode(defs, grid);
@@ -124,7 +147,7 @@ int main(int argc, char** argv) {
         if (!certify_path.empty() && !hist.empty() && hist.back().result == SolverResult::Unsat && !g_interrupted.load()) {
             PlatformLimits bound = limits;
             if (hist.back().k != (size_t)-1) bound.card_limits[Dims{1, 1}] = hist.back().k;
-            if (!certify(enc.with_limits(bound).into_cnf(), opts, certify_path, honour_deletions)) return 1;
+            if (!certify(enc.with_limits(bound).into_cnf(), opts, certify_path, honour_deletions, verify)) return 1;
         }
         return hist.empty() ? 1 : 0;
     } catch (const std::exception& e) {

@@ -450,6 +450,14 @@ struct mi355sat {
         std::vector<MsState> base;             // the workers' counters when the last solve ended (they run on)
         mi355sat_incremental_info info{};
     } inc;
+    // What the last mi355sat_check_lrat found every line of a file to rest on (mi355sat_lrat_used): caller clause indices,
+    // ascending; valid after a call with accepted == 1 until the next one or a clause added.  Test hook
+    // (mi355sat_debug_lrat_chunk): lines per launch, 0 = the rule.
+    struct Lrat {
+        bool valid = false;
+        std::vector<uint64_t> used;
+    } lrat;
+    uint32_t lrat_chunk = 0;
     DevBuf<int32_t> d_inc_lits;
     DevBuf<uint32_t> d_inc_offs;
     // phase hints (mi355sat_phase / mi355sat_set_phases): kept on the handle in the caller's variables; every cold start maps
@@ -3558,6 +3566,275 @@ int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_
     return rc;
 }
 
+// ---- strict LRAT check (mi355sat_check_lrat) ------------------------------------------------------------------------------
+// Host side of ms_lrat_kernel.  The file is parsed and validated before anything is uploaded; what is not LRAT at all is
+// MI355SAT_ERR_ARG.  The database is the caller's clauses as they were added (no simplification, the caller's variables)
+// with the file's lines behind them; every hint id is rewritten to a clause index of that database by binary search over
+// the increasing line ids - an id that names neither an original nor an EARLIER line becomes MS_LRAT_NONE, which the device
+// reports when the hint's turn comes.  The first line whose id is not above its predecessor's (the originals' for the
+// first) ends what is uploaded: it is the first rejected line unless an earlier one is.  Lines go to the device in file
+// order, in chunks; the first chunk with a rejection ends the call.  The call owns its device buffers and leaves the worker
+// slabs, and with them everything a solve, a trim or the IPASIR state keeps, alone.  DESIGN.md §4.
+struct LratFile {
+    std::vector<uint64_t> ids;             // per line, as written
+    std::vector<int32_t> lits;             // DIMACS literals line by line
+    std::vector<uint64_t> loffs{0};
+    std::vector<uint64_t> hints;           // ids as written, all > 0
+    std::vector<uint64_t> hoffs{0};
+};
+
+// lines: flat words `id, literals, 0, hints, 0` (W = int32_t: the caller's array; int64_t: a text file's numbers).
+template <class W>
+int parse_lrat_words(mi355sat& s, const W* w, uint64_t n, LratFile& F) {
+    uint64_t i = 0;
+    while (i < n) {
+        const int64_t id = (int64_t)w[i++];
+        if (id <= 0) { s.err = id == INT32_MIN ? "lrat: a deletion marker" : "lrat: a line's id is not positive"; return MI355SAT_ERR_ARG; }
+        for (; i < n && w[i] != 0; i++) {
+            const int64_t l = (int64_t)w[i];
+            if (l <= INT32_MIN || l > INT32_MAX) { s.err = "lrat: a literal out of range"; return MI355SAT_ERR_ARG; }
+            if (var_of((int32_t)l) > s.max_var) { s.err = "lrat: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
+            F.lits.push_back((int32_t)l);
+        }
+        if (i == n) { s.err = "lrat: a line's clause is not terminated"; return MI355SAT_ERR_ARG; }
+        i++;
+        for (; i < n && w[i] != 0; i++) {
+            if ((int64_t)w[i] < 0) { s.err = "lrat: a negative hint"; return MI355SAT_ERR_ARG; }
+            F.hints.push_back((uint64_t)w[i]);
+        }
+        if (i == n) { s.err = "lrat: the last line's hints are not terminated"; return MI355SAT_ERR_ARG; }
+        i++;
+        F.ids.push_back((uint64_t)id);
+        F.loffs.push_back(F.lits.size());
+        F.hoffs.push_back(F.hints.size());
+    }
+    return 0;
+}
+
+// LRAT text, one line per clause -> the flat words.  A line must be whole: integers only (so `id d ...` is refused), the
+// clause's 0, hints without a 0 among them, the closing 0.
+int read_lrat_file(mi355sat& s, const char* path, std::vector<int64_t>& words) {
+    FILE* f = fopen(path, "r");
+    if (!f) { s.err = std::string("cannot open LRAT file ") + path; return MI355SAT_ERR_ARG; }
+    std::string text;
+    char buf[1 << 16];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+    fclose(f);
+    const char* p = text.c_str();
+    const char* const end_text = p + text.size();
+    uint64_t line_no = 0;
+    while (p < end_text) {
+        line_no++;
+        const size_t first = words.size();
+        size_t zeros = 0;
+        for (;;) {
+            while (*p == ' ' || *p == '\t' || *p == '\r') p++;
+            if (*p == '\n' || p >= end_text) break;
+            char* end = nullptr;
+            const long long v = strtoll(p, &end, 10);
+            const bool whole = end != p && (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n' || end >= end_text);
+            if (!whole || v < -(1ll << 62) || v > (1ll << 62)) {
+                s.err = "lrat: line " + std::to_string(line_no) + (*p == 'd' ? " is a deletion line" : " is not a line of integers");
+                return MI355SAT_ERR_ARG;
+            }
+            words.push_back(v);
+            zeros += v == 0;
+            p = end;
+        }
+        if (p < end_text) p++;      // the '\n'
+        const size_t n = words.size() - first;
+        if (n == 0) continue;
+        // id, literals, 0, hints, 0: the first 0 behind the id ends the clause, the only other one ends the line
+        if (words[first] <= 0) { s.err = "lrat: line " + std::to_string(line_no) + " has no positive id"; return MI355SAT_ERR_ARG; }
+        if (n < 3 || words.back() != 0 || zeros != 2) {
+            s.err = "lrat: line " + std::to_string(line_no) + (zeros > 2 ? " has a 0 among its hints" : " is not terminated");
+            return MI355SAT_ERR_ARG;
+        }
+    }
+    return 0;
+}
+
+inline bool same_literal_set(std::vector<int32_t> a, std::vector<int32_t> b) {
+    std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end());
+    std::sort(b.begin(), b.end()); b.erase(std::unique(b.begin(), b.end()), b.end());
+    return a == b;
+}
+
+// Which build of ms_lrat_kernel runs: the assignment map in LDS (2 bits per variable, one wavefront per workgroup) when
+// opts.lds_val forces it and a workgroup may have that much (64 KB), or on auto when 16 workgroups per CU fit the 150 KB the
+// search builds budget; else one word per variable and wave in HBM.
+inline uint32_t lrat_map_bytes(uint32_t n_vars) { return (uint32_t)align_up((size_t)((n_vars + 15) / 16) * 4, 16); }
+inline bool lrat_in_lds(int opt_lds_val, uint32_t map_bytes) {
+    if (opt_lds_val < 0) return false;
+    return map_bytes <= (opt_lds_val > 0 ? 64u * 1024 : 150u * 1024 / 16);
+}
+
+int check_lrat_impl(mi355sat& s, const LratFile& F, const int32_t* target, uint64_t n_target, mi355sat_lrat_info& info) {
+    for (uint64_t i = 0; i < n_target; i++) {
+        if (target[i] == 0 || target[i] == INT32_MIN) { s.err = "lrat target: literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
+        if (var_of(target[i]) > s.max_var) { s.err = "lrat target: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
+    }
+    const uint64_t n_orig = s.offs.size() - 1, n_lines = F.ids.size();
+    info.n_lines = n_lines;
+    info.n_hints = F.hints.size();
+    // the target: a tautology needs no line; else the last line must be it
+    const std::vector<int32_t> tg(target, target + n_target);
+    bool taut = false;
+    for (int32_t l : tg) taut = taut || std::find(tg.begin(), tg.end(), -l) != tg.end();
+    if (taut) info.derives_target = 1;
+    else if (n_lines) info.derives_target = same_literal_set(tg, std::vector<int32_t>(F.lits.begin() + F.loffs[n_lines - 1], F.lits.end())) ? 1 : 0;
+    // the lines whose ids are in order: [0, n_up)
+    uint64_t n_up = 0;
+    for (uint64_t last = n_orig; n_up < n_lines && F.ids[n_up] > last; n_up++) last = F.ids[n_up];
+    const uint64_t n_db_lits = s.lits.size() + F.loffs[n_up];
+    // (the kernel forms `offset + lane` in 32 bits: the last offset stays a wavefront and more below 2^32)
+    if (n_orig + n_up + 2 > 0xffffff00ull || n_up + 2 > (1ull << 30) || n_db_lits > 0xffffff00ull || F.hoffs[n_up] > 0xffffff00ull) {
+        s.err = "lrat: the file is too large for the device's 32-bit indices";
+        return MI355SAT_ERR_OOM;
+    }
+    const uint32_t n_vars = (uint32_t)std::max<uint64_t>(1, s.max_var);
+    const uint32_t map_bytes = lrat_map_bytes(n_vars);
+    const bool lds = lrat_in_lds(s.opts.lds_val, map_bytes);
+    info.lds = lds ? 1 : 0;
+    info.dyn_lds_bytes = lds ? map_bytes : 0;
+    // the database: originals, then the lines; the hints as clause indices
+    std::vector<int32_t> dl;
+    std::vector<uint32_t> doff{0};
+    dl.reserve(n_db_lits);
+    doff.reserve(n_orig + n_up + 1);
+    for (uint64_t c = 0; c < n_orig; c++) {
+        for (uint64_t k = s.offs[c]; k < s.offs[c + 1]; k++) dl.push_back(to_internal(s.lits[k]));
+        doff.push_back((uint32_t)dl.size());
+        info.longest_clause = std::max<uint64_t>(info.longest_clause, s.offs[c + 1] - s.offs[c]);
+    }
+    for (uint64_t i = 0; i < n_up; i++) {
+        for (uint64_t k = F.loffs[i]; k < F.loffs[i + 1]; k++) dl.push_back(to_internal(F.lits[k]));
+        doff.push_back((uint32_t)dl.size());
+        info.longest_clause = std::max<uint64_t>(info.longest_clause, F.loffs[i + 1] - F.loffs[i]);
+    }
+    std::vector<uint32_t> dh(F.hoffs[n_up]), dhoff(n_up + 1);
+    for (uint64_t i = 0; i < n_up; i++) {
+        dhoff[i] = (uint32_t)F.hoffs[i];
+        for (uint64_t k = F.hoffs[i]; k < F.hoffs[i + 1]; k++) {
+            const uint64_t h = F.hints[k];
+            uint32_t idx = MS_LRAT_NONE;
+            if (h <= n_orig) idx = (uint32_t)(h - 1);
+            else {      // an earlier line (ids[0, i) increase strictly, and all are below this line's own)
+                const auto it = std::lower_bound(F.ids.begin(), F.ids.begin() + i, h);
+                if (it != F.ids.begin() + i && *it == h) idx = (uint32_t)(n_orig + (uint64_t)(it - F.ids.begin()));
+            }
+            dh[k] = idx;
+        }
+    }
+    dhoff[n_up] = (uint32_t)F.hoffs[n_up];
+    uint64_t rej_line = UINT64_MAX;
+    uint32_t rej_reason = 0, rej_hint = MS_LRAT_NONE;
+    // an interrupt that came before the call stops it here, whatever the file holds - also one that needs no launch
+    bool interrupted = s.interrupted.load() != 0;
+    DevBuf<uint32_t> d_used;
+    const size_t used_words = std::max<size_t>(1, (n_orig + 31) / 32);
+    if (n_up && !interrupted) {
+        // one word per variable and wave holds the HBM build's map: at most 1 GiB of it
+        const uint32_t grid_cap = lds ? 4096u : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(64, (1ull << 28) / n_vars));
+        DevBuf<int32_t> d_lits;
+        DevBuf<uint32_t> d_offs, d_hints, d_hoffs, d_rec, d_map;
+        d_lits.upload_nonempty(dl, s.stream);
+        d_offs.upload(doff, s.stream);
+        d_hints.upload_nonempty(dh, s.stream);
+        d_hoffs.upload(dhoff, s.stream);
+        d_used.alloc(used_words);
+        HIPCHK(hipMemsetAsync(d_used.p, 0, used_words * 4, s.stream));
+        d_rec.alloc((size_t)grid_cap * 4);
+        HIPCHK(hipMemsetAsync(d_rec.p, 0xff, (size_t)grid_cap * 16, s.stream));
+        if (!lds) {
+            const size_t map_words = (size_t)std::min<uint64_t>(grid_cap, n_up) * n_vars;
+            d_map.alloc(map_words);
+            HIPCHK(hipMemsetAsync(d_map.p, 0, map_words * 4, s.stream));
+        }
+        HIPCHK(hipStreamSynchronize(s.stream));
+        MsLrat A{};
+        A.lits = d_lits.p; A.offs = d_offs.p; A.hints = d_hints.p; A.hoffs = d_hoffs.p;
+        A.used = d_used.p; A.rec = d_rec.p; A.map = d_map.p;
+        A.n_orig = (uint32_t)n_orig; A.n_vars = n_vars;
+        const double k0 = s.stats.kernel_seconds;
+        std::vector<uint32_t> rec;
+        for (uint64_t a = 0; a < n_up && rej_line == UINT64_MAX;) {
+            if (s.interrupted.load()) { interrupted = true; break; }
+            // a launch: lrat_chunk lines (the test hook), else lines until they hold 2^24 hints - about 20 ms at the 7e8
+            // hints a second measured on the rect 24 file
+            uint64_t b = a + 1;
+            if (s.lrat_chunk) b = std::min<uint64_t>(n_up, a + s.lrat_chunk);
+            else while (b < n_up && F.hoffs[b] - F.hoffs[a] < (1ull << 24)) b++;
+            const uint32_t grid = (uint32_t)std::min<uint64_t>(b - a, grid_cap);
+            A.line0 = (uint32_t)a; A.line1 = (uint32_t)b;
+            timed_launch(s, [&] {
+                with_flag(lds, [&](auto lds_build) {
+                    hipLaunchKernelGGL((ms_lrat_kernel<decltype(lds_build)::value>), dim3(grid), dim3(MS_WAVE), info.dyn_lds_bytes, s.stream, A);
+                });
+            }, [] {});
+            info.launches++;
+            info.waves = std::max<uint64_t>(info.waves, grid);
+            rec.resize((size_t)grid * 4);
+            HIPCHK(hipMemcpy(rec.data(), d_rec.p, rec.size() * 4, hipMemcpyDeviceToHost));
+            for (uint32_t w = 0; w < grid; w++)
+                if (rec[4 * w] != MS_LRAT_NONE && rec[4 * w] < rej_line) { rej_line = rec[4 * w]; rej_reason = rec[4 * w + 1]; rej_hint = rec[4 * w + 2]; }
+            a = b;
+        }
+        info.kernel_seconds = s.stats.kernel_seconds - k0;
+        if (rej_line != UINT64_MAX && (rej_line >= n_up || rej_reason < MS_LRAT_TAUTOLOGY || rej_reason > MS_LRAT_LAST_NOT_FALSIFIED)) {
+            s.err = "lrat check: the device reported a line it was not given";
+            return MI355SAT_ERR_HIP;
+        }
+    }
+    if (interrupted) {
+        consume_interrupt(s);
+        info.accepted = -1;
+        return MI355SAT_INTERRUPTED;
+    }
+    if (rej_line == UINT64_MAX && n_up < n_lines) { rej_line = n_up; rej_reason = MS_LRAT_ID_ORDER; }
+    if (rej_line != UINT64_MAX) {
+        info.first_rejected = rej_line;
+        info.first_rejected_id = F.ids[rej_line];
+        info.reason = (int32_t)rej_reason;
+        info.reject_hint = rej_hint == MS_LRAT_NONE ? UINT64_MAX : rej_hint;
+        return 0;
+    }
+    info.accepted = 1;
+    info.valid = info.derives_target;
+    if (n_up) {
+        std::vector<uint32_t> bits(used_words);
+        HIPCHK(hipMemcpy(bits.data(), d_used.p, used_words * 4, hipMemcpyDeviceToHost));
+        for (uint64_t c = 0; c < n_orig; c++) if (bits[c >> 5] >> (c & 31) & 1) s.lrat.used.push_back(c);
+    }
+    s.lrat.valid = true;
+    info.used_originals = s.lrat.used.size();
+    return 0;
+}
+
+// The one body of mi355sat_check_lrat and _check_lrat_file.
+int lrat_entry(mi355sat* s, const int32_t* words, uint64_t n_words, const char* path, const int32_t* target, uint64_t n_target,
+               mi355sat_lrat_info* out) {
+    mi355sat_lrat_info info{};
+    info.first_rejected = info.reject_hint = UINT64_MAX;
+    *out = info;                        // (every refusal below leaves it so)
+    s->lrat = mi355sat::Lrat();         // the result of the check before ends here, also when this one is refused
+    if (s->sweep) { s->err = "check_lrat() called during a sweep"; return MI355SAT_ERR_STATE; }
+    if (!s->pending.empty()) { s->err = "check_lrat() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
+    LratFile F;
+    const double t0 = now_s();          // (info.seconds is the whole call: reading and parsing the text is most of it)
+    if (int rc = guarded(s, GUARD_HOST, [&] {
+            std::vector<int64_t> text;
+            if (!path) return parse_lrat_words(*s, words, n_words, F);
+            if (int e = read_lrat_file(*s, path, text)) return e;
+            return parse_lrat_words(*s, text.data(), text.size(), F);
+        })) return rc;
+    const int rc = guarded(s, GUARD_TIMED, [&] { return check_lrat_impl(*s, F, target, n_target, info); });
+    if (rc < 0) s->lrat = mi355sat::Lrat();
+    info.seconds = now_s() - t0;
+    *out = info;
+    return rc;
+}
+
 }  // namespace
 
 struct SweepHolder { Sweep sw; mi355sat_stats_t base; };
@@ -3660,6 +3937,7 @@ static int add_clause_impl(mi355sat* s, const int32_t* l, uint64_t n) {
     s->offs.push_back(s->lits.size());
     s->core.valid = false;     // IPASIR: adding leaves the UNSAT state
     s->trim.drop();            // (clause indices mean something else now)
+    s->lrat = mi355sat::Lrat();
     s->stats.n_clauses++;
     s->stats.max_var = s->max_var;
     s->stats.avg_clause_len = (double)s->lits.size() / (double)s->stats.n_clauses;
@@ -3923,6 +4201,32 @@ int mi355sat_trim_write_lrat(mi355sat* s, const char* path) { return write_trimm
 int mi355sat_debug_trim_log(mi355sat* s, uint32_t words_per_worker) {
     if (!s) return MI355SAT_ERR_ARG;
     s->trim_log_words = words_per_worker;
+    return 0;
+}
+
+int mi355sat_check_lrat(mi355sat* s, const int32_t* lines, uint64_t n_words, const int32_t* target, uint64_t n_target,
+                        mi355sat_lrat_info* out) {
+    if (!s || !out || (n_words && !lines) || (n_target && !target)) return MI355SAT_ERR_ARG;
+    return lrat_entry(s, lines, n_words, nullptr, target, n_target, out);
+}
+
+int mi355sat_check_lrat_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, mi355sat_lrat_info* out) {
+    if (!s || !out || !path || (n_target && !target)) return MI355SAT_ERR_ARG;
+    return lrat_entry(s, nullptr, 0, path, target, n_target, out);
+}
+
+int mi355sat_lrat_used(mi355sat* s, uint64_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (!s->lrat.valid) {
+        s->err = "no checked LRAT file: the last call was not a mi355sat_check_lrat() that accepted every line";
+        return MI355SAT_ERR_STATE;
+    }
+    return copy_indices(s, s->lrat.used, out, cap, n);
+}
+
+int mi355sat_debug_lrat_chunk(mi355sat* s, uint32_t max_lines_per_launch) {
+    if (!s) return MI355SAT_ERR_ARG;
+    s->lrat_chunk = max_lines_per_launch;
     return 0;
 }
 

@@ -149,6 +149,37 @@ class Mi355SatProofDelInfo(ctypes.Structure):   # mi355sat_proof_del_info
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LratReason(enum.IntEnum):  # MI355SAT_LRAT_*: why check_lrat rejected a line
+    NONE = 0
+    ID_ORDER = 1
+    TAUTOLOGY = 2
+    NO_HINTS = 3
+    BAD_HINT = 4
+    HINT_SATISFIED = 5
+    HINT_NOT_UNIT = 6
+    HINT_FALSIFIED_EARLY = 7
+    LAST_NOT_FALSIFIED = 8
+
+
+class Mi355SatLratInfo(ctypes.Structure):   # mi355sat_lrat_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("valid", "accepted", "derives_target", "reason")] + \
+               [(n, ctypes.c_uint64) for n in ("n_lines", "n_hints", "first_rejected", "first_rejected_id", "reject_hint",
+                                               "used_originals", "longest_clause")] + \
+               [("lds", ctypes.c_int32), ("dyn_lds_bytes", ctypes.c_uint32), ("waves", ctypes.c_uint64), ("launches", ctypes.c_uint64),
+                ("seconds", ctypes.c_double), ("kernel_seconds", ctypes.c_double)]
+
+    def as_dict(self):
+        """first_rejected / first_rejected_id / reject_hint: None where there is none; interrupted: the check was stopped
+        and there is no verdict (accepted = -1)."""
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        if d["first_rejected"] == 2 ** 64 - 1:
+            d["first_rejected"] = d["first_rejected_id"] = None
+        if d["reject_hint"] == 2 ** 64 - 1:
+            d["reject_hint"] = None
+        d["interrupted"] = d["accepted"] < 0
+        return d
+
+
 TRIM_HINTS = 1   # MI355SAT_TRIM_HINTS
 
 
@@ -232,6 +263,10 @@ def _bind(L):
     L.mi355sat_trim_write_drup.argtypes = [vp, ctypes.c_char_p]
     L.mi355sat_trim_write_lrat.argtypes = [vp, ctypes.c_char_p]
     L.mi355sat_debug_trim_log.argtypes = [vp, ctypes.c_uint32]
+    L.mi355sat_check_lrat.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(Mi355SatLratInfo)]
+    L.mi355sat_check_lrat_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.POINTER(Mi355SatLratInfo)]
+    L.mi355sat_lrat_used.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_debug_lrat_chunk.argtypes = [vp, ctypes.c_uint32]
     L.mi355sat_set_incremental.argtypes = [vp, ctypes.c_int]
     L.mi355sat_debug_incremental.argtypes = [vp, ctypes.POINTER(Mi355SatIncrementalInfo)]
     L.mi355sat_debug_heuristics.argtypes = [vp, ctypes.POINTER(Mi355SatHeuristicsInfo)]
@@ -474,6 +509,36 @@ class Mi355Sat:
     def debug_trim_log(self, words=0):
         """Test hook: words per worker of trim_proof's dependency log (0 = the rule; never below two items of the largest size)."""
         self._check(self._L.mi355sat_debug_trim_log(self._h, int(words)), "debug_trim_log")
+
+    # ---- LRAT files checked on the device (include/mi355sat.h)
+    def check_lrat(self, lines, target=()):
+        """Strict LRAT check of `lines` - flat int32, `id, literals, 0, hints, 0` per line - against this handle's clauses
+        (clause i, 0-based, has id i + 1); `target` is the clause the last line must be (default: the empty clause).
+        Returns mi355sat_lrat_info as a dict: "accepted" 1 / 0 / -1 (interrupted), "valid" = accepted and the target
+        derived, "first_rejected" / "reason" (LratReason) / "reject_hint" of the first rejected line, None where there is
+        none.  What is not LRAT at all raises SolverError (ERR_ARG)."""
+        ln = np.ascontiguousarray(lines, dtype=np.int32)
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatLratInfo()
+        self._check(self._L.mi355sat_check_lrat(self._h, _p(ln), ln.size, _p(tg), tg.size, ctypes.byref(info)), "check_lrat")
+        return info.as_dict()
+
+    def check_lrat_file(self, path, target=()):
+        """The same for an LRAT text file as trim_write_lrat() writes it."""
+        tg = np.ascontiguousarray(list(target), dtype=np.int32)
+        info = Mi355SatLratInfo()
+        self._check(self._L.mi355sat_check_lrat_file(self._h, str(path).encode(), _p(tg), tg.size, ctypes.byref(info)),
+                    "check_lrat_file")
+        return info.as_dict()
+
+    def lrat_used(self):
+        """After a check_lrat() that accepted every line: the 0-based indices of this handle's clauses some line hinted,
+        ascending.  Raises SolverError (ERR_STATE) in any other state."""
+        return self._indices(self._L.mi355sat_lrat_used, "lrat_used")
+
+    def debug_lrat_chunk(self, max_lines_per_launch=0):
+        """Test hook: at most this many lines per launch of check_lrat (0 = the default)."""
+        self._check(self._L.mi355sat_debug_lrat_chunk(self._h, int(max_lines_per_launch)), "debug_lrat_chunk")
 
     # ---- phase hints (rustsat PhaseLit's place; seeded, not forced: include/mi355sat.h)
     def phase(self, lit):
