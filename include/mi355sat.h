@@ -556,8 +556,39 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
  * simplification derived, then after every kernel slice the clauses each worker learnt in it; every line is a
  * RUP consequence of the lines before it (the exchange only hands on clauses of earlier slices).  Deletion lines
  * ("d ...") are written for the clauses a worker drops when it reduces its clause database - except those another
- * worker may hold a copy of (exchanged or imported ones).  Must be called before solve(); path NULL disables. */
+ * worker may hold a copy of (exchanged or imported ones).  Must be called before solve(); path NULL disables.
+ * A slice's logs come back in one piece: ms_proof_gather_kernel packs the non-empty logs, rewritten to the caller's
+ * literals, into one buffer and one copy fetches it (one wavefront per non-empty log; a plain solve's file is byte for
+ * byte what the copy per worker wrote before).
+ *
+ * mi355sat_solve_batch() and mi355sat_sweep_begin() .. _sweep_end() log ONE file for the whole call in the same way: the
+ * lemmas of all workers of all instances are one derivation from the caller's formula (assumptions are decisions, so a
+ * learnt clause follows from the formula alone), and behind the lemmas of the slice that decides an instance UNSAT stands
+ * one more line for it: the clause of its negated core, in the caller's literals; several in one slice in instance order.
+ * Every line is RUP with respect to the lines before it; a core line is never the subject of a deletion line.  The empty
+ * clause - the core of a formula that is refuted whatever the assumptions, by a worker or by the simplification - is
+ * written at most once per file; for a core that holds a literal and its negation (a tautology) nothing is written; an
+ * instance answered UNSAT at once when it is reopened adds no line.  So the file certifies every UNSAT verdict of the
+ * call: mi355sat_check_proof_targets_file() with the negated cores as targets checks them all in one pass, and
+ * mi355sat_trim_proof_file() works per instance, each core line being an ordinary lemma of the file.  The file is closed
+ * at the end of solve_batch, by mi355sat_sweep_end, by an error of a step (it then ends where the error came, as a failed
+ * solve()'s) and by mi355sat_free; after an interrupt or an exhausted budget it is a valid prefix.  A sweep computes
+ * final-conflict cores only while it logs a proof (mi355sat_sweep_core_of); without a path it launches what it did
+ * before.  While a proof is logged mi355sat_share_import takes no record (*n_records = 0): a foreign clause has no
+ * derivation in this file.  opts.cube_split = 1 with more than one instance is refused under a proof path, the warm
+ * incremental mode stays cold, mi355sat_minimize_core logs nothing. */
 int mi355sat_set_proof_path(mi355sat* s, const char* path);
+/* The core of an instance that has reported UNSAT in the running sweep, between mi355sat_sweep_begin and _sweep_end of a
+ * sweep that logs a proof; sizing and errors as mi355sat_core_of.  In any other state: MI355SAT_ERR_STATE. */
+int mi355sat_sweep_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n);
+/* Test hook: what writing the proof file open now (or closed last) took.  drains: calls after a slice, drain_seconds their
+ * wall time (lengths, kernel, copy, text); gathers: those that found a non-empty log and launched ms_proof_gather_kernel;
+ * logs / words: non-empty logs and words they packed; core_lines: negated cores written (the empty clause not counted). */
+typedef struct mi355sat_proof_log_info {
+    uint64_t drains, gathers, logs, words, core_lines;
+    double   drain_seconds;
+} mi355sat_proof_log_info;
+int mi355sat_debug_proof_log(const mi355sat* s, mi355sat_proof_log_info* out);
 
 /* Check a DRUP proof on the device: a certificate for an UNSAT answer (ms_rup_kernel).
  * Semantics: forward RUP with deletions ignored.  Lemma i must follow by unit propagation from the handle's clauses plus
@@ -601,6 +632,29 @@ int mi355sat_check_proof(mi355sat* s, const int32_t* proof, uint64_t n_words,
 /* The same for a DRUP text file as mi355sat_set_proof_path writes it ("d ..." = a deletion line). */
 int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target,
                               uint32_t segments, mi355sat_proof_info* out);
+/* Several targets in one pass: what certifies every UNSAT verdict of a batch or a sweep from the one file it logged
+ * (mi355sat_set_proof_path).  The lemmas are checked exactly as mi355sat_check_proof checks them; target t =
+ * targets[target_offsets[t] .. target_offsets[t + 1]) is item number n_lemmas + t.  Each target is checked against the
+ * formula plus ALL lemmas; none is ever attached, so targets do not see each other.  target_valid[t] = 1 when target t
+ * is RUP, or holds a literal and its negation, or the database is refuted by then; 0 otherwise; every entry is -1 when
+ * the call was interrupted.  out->valid = 1 iff every lemma and every target passes; first_failed is the smallest failing
+ * item, a target counting as n_lemmas + t.  refuted_at, segments (the n_lemmas + n_targets items are cut as before), the
+ * counters, the argument and state errors, "takes the device over", the interrupt and the statistics are those of
+ * mi355sat_check_proof; n_targets = 0 is MI355SAT_ERR_ARG; with n_targets = 1 every field equals what
+ * mi355sat_check_proof reports for the same inputs.  With mi355sat_proof_deletions on, all targets are checked after
+ * the last line: the deletion lines behind the last lemma are honoured once, each target is then propagated over the
+ * caller's clauses, the live lemmas and the facts, and none joins.  Trimming stays per target (mi355sat_trim_proof).
+ * Measured (MI355X, profiles/r12_sweep_proof.log): logging rect 24x24 k = 8 with 1024 workers, a solve takes
+ * 3.9-4.4 s with the gathered drain beside 5.2-5.4 s with the parent commit's copies per worker (134-144 ms per slice in
+ * the drain, nearly all of it text); a deterministic sweep of the rect 24x24 bounds 10 .. 0 takes 1064 ms per step with a
+ * proof beside 152 ms without (87 % in the drains: a file of 962 MB).  One pass over that file's 9 targets against one
+ * check per bound: unmeasured - with deletion lines ignored its 1 958 730 lemmas do not fit the checker's stores. */
+int mi355sat_check_proof_targets(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* targets,
+                                 const uint64_t* target_offsets, uint64_t n_targets, uint32_t segments,
+                                 int32_t* target_valid /* n_targets */, mi355sat_proof_info* out);
+int mi355sat_check_proof_targets_file(mi355sat* s, const char* path, const int32_t* targets, const uint64_t* target_offsets,
+                                      uint64_t n_targets, uint32_t segments, int32_t* target_valid /* n_targets */,
+                                      mi355sat_proof_info* out);
 /* Test hook: at most this many lemmas (checked or attached) per worker per launch, and no time bound; 0 = the default
  * (launches of about 20 ms). */
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch);

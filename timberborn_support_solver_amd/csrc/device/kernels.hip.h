@@ -2911,6 +2911,37 @@ __global__ __launch_bounds__(MS_WAVE) void ms_core_model_kernel(MsLayout L, cons
     if (lane == 0) ((Gp<int32_t>)ok)[b] = bad ? 0 : 1;
 }
 
+// ---- the workers' DRUP logs in one packed buffer (proof_drain) -----------------------------
+// After a slice every worker's log holds lemma words from word 0 up and deletion words from the top of its region down
+// (proof_lemma_slot, proof_log_deletions); most logs of a large fleet are empty.  The host has read the 2 * W lengths,
+// checked them against proof_cap and listed the non-empty logs as jobs of four words: worker, lemma words, deletion
+// words, and where the worker's words start in `out` (exclusive sums, worker by worker).  One workgroup (one wave) per
+// job copies the lemma words, then the deletion words in address order, 64 lanes striding: every load and store of a
+// round is one coalesced run of dwords.  On the way a literal word (>= 0, a device literal) becomes the caller's literal
+// 2 * var + sign through inv (inverse_order(perm): device variable -> caller's); the markers (-1 ends a clause, -2 opens
+// a deletion line, any negative word) pass through untouched.  A literal beyond n_vars - a log that is not one - becomes
+// MS_PROOF_BAD, which the host refuses.  Nothing but `out` is written, no two lanes write one word; no LDS, no atomics.
+#define MS_PROOF_BAD INT32_MIN
+__global__ __launch_bounds__(MS_WAVE) void ms_proof_gather_kernel(const int32_t* proof_buf, uint32_t proof_cap, const uint32_t* jobs,
+                                                                 const uint32_t* inv, uint32_t n_vars, int32_t* out) {
+    const uint32_t lane = threadIdx.x;
+    Gp<const uint32_t> job = (Gp<const uint32_t>)jobs + 4 * (size_t)blockIdx.x;
+    const uint32_t wid = (uint32_t)uni((int)job[0]), n_lem = (uint32_t)uni((int)job[1]), n_del = (uint32_t)uni((int)job[2]);
+    const uint32_t o = (uint32_t)uni((int)job[3]);
+    if (n_lem > proof_cap || n_del > proof_cap - n_lem) return;      // (the host has checked: never read beyond a region)
+    Gp<const int32_t> log = (Gp<const int32_t>)proof_buf + (size_t)wid * proof_cap;
+    Gp<const uint32_t> iv = (Gp<const uint32_t>)inv;
+    Gp<int32_t> dst = (Gp<int32_t>)out + o;
+    auto word = [&](int32_t x) -> int32_t {
+        if (x < 0) return x;
+        const uint32_t v = (uint32_t)x >> 1;
+        return v < n_vars ? (int32_t)(2u * iv[v] | ((uint32_t)x & 1u)) : MS_PROOF_BAD;
+    };
+    for (uint32_t i = lane; i < n_lem; i += MS_WAVE) dst[i] = word(log[i]);
+    Gp<const int32_t> del = log + (proof_cap - n_del);
+    for (uint32_t i = lane; i < n_del; i += MS_WAVE) dst[n_lem + i] = word(del[i]);
+}
+
 // This lane's share of a round over the clause cl[.. e), 64 literals per round, one per lane, the round starting at k0:
 // in = the lane has a literal, ok = and it is in range.  lane_value: its value, `dflt` for a lane that is not ok.
 struct ClauseLane { bool in, ok; int lit; };
@@ -3235,6 +3266,10 @@ DEV void rup_drop_dead(Wk& w, const MsShared& sh, const MsLayout& L, Gp<const ui
 //   always : attach it as ms_attach_kernel does under the level-0 assignment (satisfied: nothing; no free literal: the
 //            database is refuted from lemma j + 1 on; one: a level-0 fact left in the queue; else add_learnt with LBD 1,
 //            which no reduction ever drops).  The target is checked, never attached.
+// Several targets (mi355sat_check_proof_targets): the items n_lemmas .. n_items - 1 are all targets.  None is attached, so
+// each is checked against the formula and ALL lemmas and no target sees another; one that fails also sets its byte of
+// target_fail (the worker that owns it is the only writer).  A database that has fallen ends the worker before it reaches
+// its remaining targets: they count as valid.  The TRACE build is launched with one target only.
 // Deletion lines never reach the device: every clause in a worker's database is an original or a lemma, unit propagation
 // is monotone, so ignoring them is sound, and the verdict does not depend on the cut.  A lemma holding x and ~x is marked
 // on the host (skip[j]): never checked or attached.  No conflict is analysed, no clause is ever reduced away (the stores
@@ -3261,7 +3296,8 @@ DEV void rup_drop_dead(Wk& w, const MsShared& sh, const MsLayout& L, Gp<const ui
 template <bool LV, bool TRACE = false, bool DEL = false>
 __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L, char* slabs, MsParams prm, const int32_t* lits,
                                                         const uint32_t* offs, const uint8_t* skip, uint32_t n_items,
-                                                        unsigned long long* mins, MsTrace tr, const uint32_t* death) {
+                                                        unsigned long long* mins, MsTrace tr, const uint32_t* death,
+                                                        uint32_t n_lemmas, uint8_t* target_fail) {
     __shared__ int32_t s_ring[MS_LDS_RING];
     __shared__ uint32_t s_claim[MS_CLAIM_SLOTS];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[4 * MS_MAX_GROUPS < 64 ? 64 : 4 * MS_MAX_GROUPS];
@@ -3357,9 +3393,13 @@ __global__ __launch_bounds__(MS_WAVE) void ms_rup_kernel(MsShared sh, MsLayout L
             w.confl_kind = 0;
             if (premarks) tr_lemma_marks<LV>(w, sh, L, cl, lb, le, false);
             if (w.status != MS_ST_RUNNING) break;
-            if (!confl) note_min(0, j);
+            if (!confl) {
+                note_min(0, j);
+                // (a target is owned by exactly one worker: a plain store by one lane)
+                if (j >= n_lemmas && w.lane == 0) ((Gp<uint8_t>)target_fail)[j - n_lemmas] = 1;
+            }
         }
-        if (j + 1 >= n_items) continue;               // the target: checked only
+        if (j >= n_lemmas) continue;                  // a target: checked only
         n_attached++;
         bool sat, bad;
         const int cnt = attach_scan<LV>(w, sh, L, cl, lb, le, learnt_buf, sat, bad);

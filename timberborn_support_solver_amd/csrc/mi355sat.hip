@@ -386,7 +386,13 @@ struct mi355sat {
     DevBuf<int32_t> d_any_done, d_assump, d_script, d_proof;
     DevBuf<uint32_t> d_proof_len;
     uint32_t proof_cap = 0;                    // words per worker in d_proof
-    FILE* proof_file = nullptr;                // open while a solve logs its DRUP proof
+    FILE* proof_file = nullptr;                // open while a solve, a batch or a sweep logs its DRUP proof
+    bool proof_empty = false;                  // the open file holds the empty clause already (written at most once)
+    // proof_drain: the non-empty logs as jobs, the packed words (ms_proof_gather_kernel) - both grow when needed and stay -
+    // and inverse_order(perm) of the cold start that allocated the logs
+    DevBuf<uint32_t> d_proof_jobs, d_proof_inv;
+    DevBuf<int32_t> d_proof_out;
+    mi355sat_proof_log_info proof_log{};       // test hook (mi355sat_debug_proof_log): the drains since the file was opened
     DevBuf<uint64_t> d_assump_off, d_script_off;
     // learnt-clause exchange between workers (layout.h MS_SHARE_*)
     DevBuf<int32_t> d_share_pool;
@@ -1806,38 +1812,70 @@ void launch_probe(mi355sat& s) { launch_slice(s, 2, false); }
 // slice the clauses each worker learnt in it (worker by worker, each in its own derivation order), finally the empty
 // clause.  That order makes every line a RUP consequence of the lines before it: a learnt clause depends on its
 // worker's earlier clauses and on exchanged clauses, and the exchange only hands on clauses of EARLIER slices.
+// A batch or a sweep writes one such file for all its instances: the lemmas of all workers of all instances are one
+// derivation from the caller's formula (assumptions are decisions, so a learnt clause follows from the formula alone), and
+// behind the lemmas of a slice stands, for every instance that slice decided UNSAT, the clause of its negated core
+// (proof_core_lines).
 void proof_open(mi355sat& s) {
+    if (s.proof_file) fclose(s.proof_file);      // (a sweep begun over a running one)
     s.proof_file = fopen(s.proof_path.c_str(), "w");
     if (!s.proof_file) throw HipErr{"cannot open proof file " + s.proof_path};
+    s.proof_empty = false;
+    s.proof_log = mi355sat_proof_log_info{};
+    bool line_start = true;
     for (int32_t l : s.simp_proof) {   // (caller's numbering already)
-        if (l < 0) fputs("0\n", s.proof_file);
+        if (l < 0) { fputs("0\n", s.proof_file); s.proof_empty = s.proof_empty || line_start; }
         else fprintf(s.proof_file, "%d ", to_dimacs(l));
+        line_start = l < 0;
     }
 }
+// After a slice: the 2 * W lengths, the overflow rule, then ONE kernel (ms_proof_gather_kernel: a wavefront per non-empty
+// log packs its lemma words and its deletion words, rewritten to the caller's literals) and ONE copy; the host only
+// formats text.  The order in the file is the order of the packed buffer: worker by worker, lemmas then deletion lines.
 void proof_drain(mi355sat& s) {
     if (!s.proof_file || !s.d_proof_len.p) return;
+    struct Timed {       // (mi355sat_debug_proof_log: the wall time of the drains, whichever way one ends)
+        mi355sat_proof_log_info& info;
+        double t0 = now_s();
+        ~Timed() { info.drains++; info.drain_seconds += now_s() - t0; }
+    } timed{s.proof_log};
     const uint32_t W = (uint32_t)(s.d_proof_len.n / 2);     // per worker: lemma words from word 0 up, deletion words from the top down
-    std::vector<uint32_t> len(2 * (size_t)W);
+    std::vector<uint32_t> len(2 * (size_t)W), jobs;
     HIPCHK(hipMemcpy(len.data(), s.d_proof_len.p, sizeof(uint32_t) * 2 * W, hipMemcpyDeviceToHost));
-    const std::vector<uint32_t> inv = inverse_order(s.perm);
-    std::vector<int32_t> buf;
-    bool any = false;
+    uint64_t total = 0;
     for (uint32_t w = 0; w < W; w++) {
         const uint32_t n_lem = len[2 * w], n_del = len[2 * w + 1];
         if (!n_lem && !n_del) continue;
-        any = true;
         if (n_lem > s.proof_cap || n_del > s.proof_cap - n_lem)
             throw HipErr{"proof buffer overflow (a worker learnt more in one slice than its log holds)", MI355SAT_ERR_OOM};
-        buf.resize((size_t)n_lem + n_del);     // the lemmas, then the deletion lines
-        if (n_lem) HIPCHK(hipMemcpy(buf.data(), s.d_proof.p + (size_t)w * s.proof_cap, sizeof(int32_t) * n_lem, hipMemcpyDeviceToHost));
-        if (n_del) HIPCHK(hipMemcpy(buf.data() + n_lem, s.d_proof.p + (size_t)w * s.proof_cap + (s.proof_cap - n_del), sizeof(int32_t) * n_del, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < buf.size(); i++) {
-            if (buf[i] == -2) fputs("d ", s.proof_file);       // deletion line
-            else if (buf[i] < 0) fputs("0\n", s.proof_file);
-            else fprintf(s.proof_file, "%d ", to_dimacs(inv, buf[i]));
-        }
+        jobs.insert(jobs.end(), {w, n_lem, n_del, (uint32_t)total});
+        total += (uint64_t)n_lem + n_del;
+        if (total > 0xffffffffull) throw HipErr{"proof buffer overflow (one slice's logs exceed 2^32 words)", MI355SAT_ERR_OOM};
     }
-    if (any) { HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * W, s.stream)); HIPCHK(hipStreamSynchronize(s.stream)); }
+    if (jobs.empty()) return;
+    if (s.d_proof_jobs.n < jobs.size()) s.d_proof_jobs.alloc(jobs.size() + jobs.size() / 2);
+    if (s.d_proof_out.n < total) s.d_proof_out.alloc((size_t)(total + total / 2));
+    HIPCHK(hipMemcpyAsync(s.d_proof_jobs.p, jobs.data(), sizeof(uint32_t) * jobs.size(), hipMemcpyHostToDevice, s.stream));
+    hipLaunchKernelGGL(ms_proof_gather_kernel, dim3((uint32_t)(jobs.size() / 4)), dim3(MS_WAVE), 0, s.stream, (const int32_t*)s.d_proof.p,
+                       s.proof_cap, (const uint32_t*)s.d_proof_jobs.p, (const uint32_t*)s.d_proof_inv.p, (uint32_t)s.d_proof_inv.n, s.d_proof_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * W, s.stream));
+    std::vector<int32_t> buf((size_t)total);
+    HIPCHK(hipMemcpyAsync(buf.data(), s.d_proof_out.p, sizeof(int32_t) * buf.size(), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    std::string text;
+    text.reserve(buf.size() * 7);
+    char num[16];
+    for (int32_t x : buf) {
+        if (x == MS_PROOF_BAD) throw HipErr{"device solver internal error (a proof log holds a literal out of range)"};
+        if (x == -2) text += "d ";             // deletion line
+        else if (x < 0) text += "0\n";
+        else { text.append(num, (size_t)snprintf(num, sizeof num, "%d ", to_dimacs(x))); }
+    }
+    fwrite(text.data(), 1, text.size(), s.proof_file);
+    s.proof_log.gathers++;
+    s.proof_log.logs += jobs.size() / 4;
+    s.proof_log.words += total;
 }
 // An UNSAT answer ends the proof with the clause of the negated core: under assumptions, what the formula implies about
 // them; without any (or when the formula itself is refuted), the empty clause.
@@ -1919,11 +1957,22 @@ struct Sweep {
     std::vector<uint32_t> open;                  // per instance: its busy workers (with splitting: its open cubes)
     uint64_t n_splits = 0, n_closed = 0;
     DevBuf<int32_t> d_upd, d_data;
-    // failed-assumption cores (solve() and solve_batch() only; the public sweep API launches nothing for them): per
-    // instance, one flag per entry of the caller's assumption list
+    // failed-assumption cores (solve(), solve_batch(), and the public sweep API while it logs a proof - without one it
+    // launches nothing for them): per instance, one flag per entry of the caller's assumption list
     bool cores = false;
     std::vector<uint32_t> base_src;              // per entry of base_assump: its index in the caller's list of the instance
     std::vector<std::vector<uint8_t>> core_flag;
+    // a batch or a sweep that logs a proof (sweep_begin): the caller's lists, and per instance "its core line is written"
+    bool log_cores = false;
+    std::vector<int32_t> caller_assump;
+    std::vector<uint64_t> caller_off;
+    std::vector<uint8_t> core_logged;
+    std::vector<int32_t> core_of(uint32_t inst) const {      // (log_cores) the caller's literals an UNSAT verdict rests on
+        std::vector<int32_t> c;
+        for (uint64_t k = 0; k < core_flag[inst].size(); k++)
+            if (core_flag[inst][k]) c.push_back(caller_assump[caller_off[inst] + k]);
+        return c;
+    }
     DevBuf<int32_t> d_fw, d_fok;
     DevBuf<uint32_t> d_fout, d_fscratch;
     DevBuf<int32_t> d_qlits;                     // core minimisation: what ms_core_model_kernel looks up (core_models)
@@ -1979,6 +2028,7 @@ struct Sweep {
         winner.assign(n, -1);
         dropped.assign(n, 0);
         core_flag.assign(cores ? n : 0, {});
+        core_logged.assign(log_cores ? n : 0, 0);
         for (uint32_t i = 0; i < n; i++) pose(i, assump_off[i + 1] - assump_off[i]);
     }
 
@@ -2102,10 +2152,40 @@ uint32_t ramp_target(const mi355sat& s, const Sweep& sw, uint32_t fleet) {
     return std::min(fleet, std::max(want, n) / n * n);
 }
 
+// (a batch or a sweep that logs a proof) One line - the negated core, in the caller's literals - for every instance that
+// is UNSAT and has none yet, in instance order: behind the lemmas of the slice that decided them (sweep_step), or behind
+// what the simplification derived when that refuted the formula (sweep_begin).  The line is RUP where it stands: the
+// deciding worker's clauses are in the file, and its final conflict follows from them under the core by propagation.
+// The empty clause - the core of a formula that is refuted itself, by a worker or by the simplification - is written once
+// per file; a core that holds a literal and its negation gives a tautology, and nothing is written for it.  An instance
+// answered UNSAT "at once" when it is reopened (Sweep::reopen) has the empty core: no line.
+void proof_core_lines(mi355sat& s, Sweep& sw) {
+    if (!s.proof_file || !sw.log_cores) return;
+    auto empty_clause = [&] {
+        if (!s.proof_empty) fputs("0\n", s.proof_file);
+        s.proof_empty = true;
+    };
+    if (sw.formula_unsat) empty_clause();        // (also when no instance was open to take the verdict)
+    for (uint32_t i = 0; i < sw.n_instances; i++) {
+        if (sw.results[i] != MI355SAT_UNSAT || sw.core_logged[i]) continue;
+        sw.core_logged[i] = 1;
+        std::vector<int32_t> core = sw.core_of(i), sorted;
+        if (core.empty()) { empty_clause(); continue; }
+        sorted = core;
+        std::sort(sorted.begin(), sorted.end(), [](int32_t a, int32_t b) { return var_of(a) != var_of(b) ? var_of(a) < var_of(b) : a < b; });
+        bool taut = false;
+        for (size_t k = 0; k + 1 < sorted.size(); k++) taut = taut || sorted[k] == -sorted[k + 1];
+        if (taut) continue;
+        for (int32_t l : core) fprintf(s.proof_file, "%d ", -l);
+        fputs("0\n", s.proof_file);
+        s.proof_log.core_lines++;
+    }
+}
+
 // keep (may be null): caller's literals whose variables must survive the simplification besides the assumptions' - lists
 // that sweep_repose will pose later; their number is also the room the slabs leave for an assumption list.
 int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, const std::vector<uint64_t>& assump_off,
-                uint32_t n_instances, bool stop_at_first, const std::vector<int32_t>* keep = nullptr) {
+                uint32_t n_instances, bool stop_at_first, const std::vector<int32_t>* keep = nullptr, bool plain_solve = false) {
     Prepared P;
     {
         Formula F;
@@ -2130,14 +2210,18 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         s.stats.simp_clauses_removed = F.n_subsumed + F.n_strengthened;
     }
     if (!s.proof_path.empty()) {
-        if (n_instances != 1) throw HipErr{"a proof can only be logged for a plain solve()"};
+        if (n_instances != 1 && s.opts.cube_split > 0) throw HipErr{"a proof can only be logged for a plain solve()"};
         proof_open(s);
+        // (a plain solve ends its file itself, with the core mi355sat_solve reports: proof_close)
+        sw.log_cores = sw.cores && !plain_solve;
+        if (sw.log_cores) { sw.caller_assump = assump; sw.caller_off = assump_off; }
     }
     sw.reset(n_instances, stop_at_first, assump_off);
     s.ph.on_device = false;              // (the mapping of the hints on the device was the last upload's)
     if (P.unsat) {
         for (uint32_t i = 0; i < n_instances; i++) sw.decide(i, MI355SAT_UNSAT, -1);
         s.trivially_unsat = true;
+        proof_core_lines(s, sw);
         return 0;
     }
     // default fleet: the whole GPU (16 waves per CU) for large formulas; mid-size ones measured fastest to a verdict
@@ -2170,6 +2254,7 @@ int sweep_begin(mi355sat& s, Sweep& sw, const std::vector<int32_t>& assump, cons
         s.d_proof.alloc((size_t)s.n_workers * s.proof_cap);
         s.d_proof_len.alloc(2 * (size_t)s.n_workers);
         HIPCHK(hipMemsetAsync(s.d_proof_len.p, 0, sizeof(uint32_t) * 2 * s.n_workers, s.stream));
+        s.d_proof_inv.upload(inverse_order(P.perm), s.stream);      // (what ms_proof_gather_kernel maps a log's literals through)
     }
     s.cap_info = mi355sat_capacity_info{};
     s.cap_info.learnt_cap = s.L.learnt_cap; s.cap_info.learnt_lit_cap = s.L.learnt_lit_cap; s.cap_info.pool_cap = s.L.pool_cap;
@@ -2579,6 +2664,7 @@ int sweep_step(mi355sat& s, Sweep& sw) {
     if (rc) return rc;
     // 4. cores - before any slab's assumptions are rewritten below - and who works on what in the next slice
     if (!fw.empty() && (rc = final_cores(s, sw, fw)) != 0) return rc;
+    proof_core_lines(s, sw);
     HIPCHK(hipMemsetAsync(s.d_any_done.p, 0, sizeof(int32_t), s.stream));
     if (sw.decided < n_instances && !(sw.stop_at_first && sw.decided > 0)) {
         if (sw.split) schedule_cubes(s, sw);
@@ -2661,7 +2747,7 @@ int run_search(mi355sat& s, const std::vector<int32_t>& assump, const std::vecto
             I.info.last_cold_reason = why;
         }
         go_cold(s, plain_solve ? MI355SAT_COLD_FIRST : MI355SAT_COLD_OTHER_SEARCH);
-        rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first);
+        rc = sweep_begin(s, sw, assump, assump_off, n_instances, stop_at_first, nullptr, plain_solve);
         if (sw.keep_warm && !rc && s.trivially_unsat) I.refuted = true;
         uploaded = sw.keep_warm && !rc && !s.trivially_unsat;
         if (uploaded) {     // what these workers know: the formula as it stands, nothing attached
@@ -2935,11 +3021,22 @@ struct ProofLemmas {
     std::vector<uint64_t> del_offs{0}, del_at;
 };
 
+// The clauses a check must derive: target t = lits[offs[t] .. offs[t + 1]), DIMACS literals; valid (may be null) receives
+// one verdict per target (mi355sat_check_proof_targets).  mi355sat_check_proof's one target is the case n = 1.
+struct ProofTargets {
+    const int32_t* lits;
+    const uint64_t* offs;
+    uint64_t n;
+    int32_t* valid;
+};
+
 // One check as it passes from stage to stage of check_proof_impl.
 struct ProofCheck {
-    ProofLemmas& pf;                   // the proof; proof_target appends the target as item n_lemmas
+    ProofLemmas& pf;                   // the proof; proof_target appends the targets as items n_lemmas ..
     mi355sat_proof_info& info;
-    uint32_t n_items = 0;              // the lemmas and the target
+    const ProofTargets& tg;
+    uint32_t n_items = 0, n_targets = 0;   // the lemmas and the targets; the targets
+    DevBuf<uint8_t> d_tfail;           // per target: a worker found it not RUP
     Prepared P;                        // the caller's clauses: not simplified, in the caller's variable order
     // the proof as the device reads it (proof_device_form)
     std::vector<int32_t> dl;           // device literals item by item, each variable at most once per item
@@ -3034,7 +3131,7 @@ SliceResult launch_rup(mi355sat& s, const ProofCheck& C, const MsTrace& mt) {
                     hipLaunchKernelGGL((ms_rup_kernel<decltype(lds_build)::value, decltype(traced)::value, decltype(deleting)::value>), dim3(active),
                                        dim3(MS_WAVE), build.dyn_lds_bytes, s.stream, s.sh, s.L, s.d_slabs.p, prm, (const int32_t*)C.d_lits.p,
                                        (const uint32_t*)C.d_offs.p, (const uint8_t*)C.d_skip.p, C.n_items, C.d_mins.p, mt,
-                                       (const uint32_t*)C.d_death.p);
+                                       (const uint32_t*)C.d_death.p, C.n_items - C.n_targets, C.d_tfail.p);
                 });
             });
         });
@@ -3269,19 +3366,25 @@ int trim_finish(mi355sat& s, TrimRun& T, const ProofCheck& C) {
 
 // ---- the stages of a check (check_proof_impl runs them in this order) ----------------------------------------------------------
 // 1. The target: validated, appended as the last item; the sizes a worker's clause store can index.
-int proof_target(mi355sat& s, ProofCheck& C, const int32_t* target, uint64_t n_target) {
+int proof_target(mi355sat& s, ProofCheck& C) {
     ProofLemmas& pf = C.pf;
+    const ProofTargets& tg = C.tg;
+    const int32_t* target = tg.lits + (tg.n ? tg.offs[0] : 0);
+    const uint64_t n_target = tg.offs[tg.n] - tg.offs[0];
+    for (uint64_t t = 0; t < tg.n; t++)
+        if (tg.offs[t + 1] < tg.offs[t]) { s.err = "proof target: offsets not monotone"; return MI355SAT_ERR_ARG; }
     for (uint64_t i = 0; i < n_target; i++) {
         if (target[i] == 0 || target[i] == INT32_MIN) { s.err = "proof target: literal 0 inside a clause"; return MI355SAT_ERR_ARG; }
         if (var_of(target[i]) > s.max_var) { s.err = "proof target: a variable the handle does not have"; return MI355SAT_ERR_ARG; }
     }
-    if (pf.n_lemmas + 2 > 0x7fffffffull || pf.lits.size() + n_target + 5 * (pf.n_lemmas + 2) > 0x7ffffff0ull) {
+    if (pf.n_lemmas + tg.n + 1 > 0x7fffffffull || pf.lits.size() + n_target + 5 * (pf.n_lemmas + tg.n + 1) > 0x7ffffff0ull) {
         s.err = "proof too large for a worker's clause store";
         return MI355SAT_ERR_OOM;
     }
     pf.lits.insert(pf.lits.end(), target, target + n_target);
-    pf.offs.push_back(pf.lits.size());
-    C.n_items = (uint32_t)pf.n_lemmas + 1;       // the target is lemma number n_lemmas
+    for (uint64_t t = 0; t < tg.n; t++) pf.offs.push_back(pf.offs[pf.n_lemmas] + (tg.offs[t + 1] - tg.offs[0]));
+    C.n_targets = (uint32_t)tg.n;
+    C.n_items = (uint32_t)(pf.n_lemmas + tg.n);  // target t is item number n_lemmas + t
     C.info.n_lemmas = pf.n_lemmas;
     C.info.n_deletions_ignored = pf.n_deletions;
     C.info.first_failed = C.info.refuted_at = UINT64_MAX;
@@ -3420,7 +3523,7 @@ void proof_device_form(ProofCheck& C) {
         if (C.skip[j]) tmp.clear();
         C.dl.insert(C.dl.end(), tmp.begin(), tmp.end());
         C.doff.push_back((uint32_t)C.dl.size());
-        if (j + 1 < C.n_items) C.store_lits += (tmp.size() + 3) & ~(size_t)3;
+        if (j < C.n_items - C.n_targets) C.store_lits += (tmp.size() + 3) & ~(size_t)3;     // (a target takes no room)
     }
     for (int k = 0; k < 4; k++) C.dl.push_back(0);
 }
@@ -3460,6 +3563,7 @@ void proof_upload(mi355sat& s, ProofCheck& C, uint32_t segments) {
     if (C.del) for (uint32_t j = 0; j < C.n_items; j++) if (C.group[j]) flags[j] |= 2;
     C.d_skip.upload(flags, s.stream);
     C.d_mins.upload(std::vector<unsigned long long>{0ull, 0ull}, s.stream);      // complements of "none"
+    C.d_tfail.upload(std::vector<uint8_t>(C.n_targets, 0), s.stream);
 }
 
 // 5. Launches until no worker is running, the interrupt flag polled between them; a traced check's log drained after each.
@@ -3515,17 +3619,24 @@ int proof_verdict(mi355sat& s, ProofCheck& C) {
         return MI355SAT_ERR_HIP;
     }
     info.valid = info.first_failed == UINT64_MAX ? 1 : 0;
+    if (C.tg.valid) {
+        std::vector<uint8_t> fail(C.n_targets);
+        HIPCHK(hipMemcpy(fail.data(), C.d_tfail.p, fail.size(), hipMemcpyDeviceToHost));
+        for (uint32_t t = 0; t < C.n_targets; t++) C.tg.valid[t] = fail[t] ? 0 : 1;
+    }
     return 0;
 }
 
 // T (may be null): mi355sat_trim_proof's traced check, which attaches before the launch (trim_begin), after each launch
 // (trim_drain, in proof_launches) and after a verdict "valid" (trim_finish).
-int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64_t n_target, uint32_t segments, mi355sat_proof_info& info,
-                     TrimRun* T) {
-    ProofCheck C{pf, info};
-    if (int rc = proof_target(s, C, target, n_target)) return rc;
+int check_proof_impl(mi355sat& s, ProofLemmas& pf, const ProofTargets& tg, uint32_t segments, mi355sat_proof_info& info, TrimRun* T) {
+    ProofCheck C{pf, info, tg};
+    if (tg.valid) std::fill(tg.valid, tg.valid + tg.n, -1);      // (what an interrupt leaves)
+    if (int rc = proof_target(s, C)) return rc;
     if (s.proof_del) proof_resolve_deletions(s, C);
-    if (!proof_without_launch(s, C)) {
+    if (proof_without_launch(s, C)) {      // refuted caller's clauses: every target holds; no variable: none does
+        if (tg.valid && info.valid >= 0) std::fill(tg.valid, tg.valid + tg.n, info.valid);
+    } else {
         proof_device_form(C);
         proof_upload(s, C, segments);
         if (T) trim_begin(s, *T, C);
@@ -3540,8 +3651,8 @@ int check_proof_impl(mi355sat& s, ProofLemmas& pf, const int32_t* target, uint64
 // The one body of mi355sat_check_proof, _trim_proof and their _file variants (name: the entry's in its messages).  The words
 // come from memory or, with a path, from a DRUP text file; trim (may be null): the traced check, whose result stays on the
 // handle, instead of the plain one that fills `out`.
-int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_words, const char* path, const int32_t* target,
-                uint64_t n_target, uint32_t segments, mi355sat_proof_info* out, mi355sat_trim_info* trim = nullptr, uint32_t flags = 0) {
+int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_words, const char* path, const ProofTargets& tg,
+                uint32_t segments, mi355sat_proof_info* out, mi355sat_trim_info* trim = nullptr, uint32_t flags = 0) {
     if (s->sweep) { s->err = std::string(name) + "() called during a sweep"; return MI355SAT_ERR_STATE; }
     if (!s->pending.empty()) { s->err = std::string(name) + "() called inside an unterminated clause"; return MI355SAT_ERR_STATE; }
     ProofLemmas pf;
@@ -3558,7 +3669,7 @@ int proof_entry(mi355sat* s, const char* name, const int32_t* words, uint64_t n_
     s->trim.drop();
     TrimRun T{flags, trim};          // (used by a trim only)
     if (trim) *trim = mi355sat_trim_info{};
-    const int rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, target, n_target, segments, info, trim ? &T : nullptr); });
+    const int rc = guarded(s, GUARD_TIMED, [&] { return check_proof_impl(*s, pf, tg, segments, info, trim ? &T : nullptr); });
     if (rc < 0 || info.valid != 1) s->trim.drop();
     info.seconds = now_s() - t0;
     if (rc < 0) go_cold(*s, MI355SAT_COLD_FIRST);
@@ -4099,16 +4210,44 @@ int mi355sat_set_proof_path(mi355sat* s, const char* path) {
     return 0;
 }
 
+int mi355sat_debug_proof_log(const mi355sat* s, mi355sat_proof_log_info* out) {
+    if (!s || !out) return MI355SAT_ERR_ARG;
+    *out = s->proof_log;
+    return 0;
+}
+
 int mi355sat_check_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
                          uint32_t segments, mi355sat_proof_info* out) {
     if (!s || !out || (n_words && !proof) || (n_target && !target)) return MI355SAT_ERR_ARG;
-    return proof_entry(s, "check_proof", proof, n_words, nullptr, target, n_target, segments, out);
+    const uint64_t toff[2] = {0, n_target};
+    return proof_entry(s, "check_proof", proof, n_words, nullptr, ProofTargets{target, toff, 1, nullptr}, segments, out);
 }
 
 int mi355sat_check_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
                               mi355sat_proof_info* out) {
     if (!s || !out || !path || (n_target && !target)) return MI355SAT_ERR_ARG;
-    return proof_entry(s, "check_proof", nullptr, 0, path, target, n_target, segments, out);
+    const uint64_t toff[2] = {0, n_target};
+    return proof_entry(s, "check_proof", nullptr, 0, path, ProofTargets{target, toff, 1, nullptr}, segments, out);
+}
+
+// (target_offsets[0] need not be 0; a target may be empty, so `targets` may be NULL when every one is)
+static bool bad_target_lists(const int32_t* targets, const uint64_t* target_offsets, uint64_t n_targets, const int32_t* target_valid) {
+    return !target_offsets || !target_valid || n_targets == 0 || (!targets && target_offsets[n_targets] > target_offsets[0]);
+}
+
+int mi355sat_check_proof_targets(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* targets,
+                                 const uint64_t* target_offsets, uint64_t n_targets, uint32_t segments, int32_t* target_valid,
+                                 mi355sat_proof_info* out) {
+    if (!s || !out || (n_words && !proof)) return MI355SAT_ERR_ARG;
+    if (bad_target_lists(targets, target_offsets, n_targets, target_valid)) { s->err = "check_proof_targets: no targets"; return MI355SAT_ERR_ARG; }
+    return proof_entry(s, "check_proof_targets", proof, n_words, nullptr, ProofTargets{targets, target_offsets, n_targets, target_valid}, segments, out);
+}
+
+int mi355sat_check_proof_targets_file(mi355sat* s, const char* path, const int32_t* targets, const uint64_t* target_offsets,
+                                      uint64_t n_targets, uint32_t segments, int32_t* target_valid, mi355sat_proof_info* out) {
+    if (!s || !out || !path) return MI355SAT_ERR_ARG;
+    if (bad_target_lists(targets, target_offsets, n_targets, target_valid)) { s->err = "check_proof_targets: no targets"; return MI355SAT_ERR_ARG; }
+    return proof_entry(s, "check_proof_targets", nullptr, 0, path, ProofTargets{targets, target_offsets, n_targets, target_valid}, segments, out);
 }
 
 int mi355sat_debug_proof_check_chunk(mi355sat* s, uint32_t max_lemmas_per_launch) {
@@ -4133,13 +4272,15 @@ int mi355sat_debug_proof_deletions(const mi355sat* s, mi355sat_proof_del_info* o
 int mi355sat_trim_proof(mi355sat* s, const int32_t* proof, uint64_t n_words, const int32_t* target, uint64_t n_target,
                         uint32_t segments, uint32_t flags, mi355sat_trim_info* out) {
     if (!s || !out || (n_words && !proof) || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
-    return proof_entry(s, "trim_proof", proof, n_words, nullptr, target, n_target, segments, nullptr, out, flags);
+    const uint64_t toff[2] = {0, n_target};
+    return proof_entry(s, "trim_proof", proof, n_words, nullptr, ProofTargets{target, toff, 1, nullptr}, segments, nullptr, out, flags);
 }
 
 int mi355sat_trim_proof_file(mi355sat* s, const char* path, const int32_t* target, uint64_t n_target, uint32_t segments,
                              uint32_t flags, mi355sat_trim_info* out) {
     if (!s || !out || !path || (n_target && !target) || (flags & ~MI355SAT_TRIM_HINTS)) return MI355SAT_ERR_ARG;
-    return proof_entry(s, "trim_proof", nullptr, 0, path, target, n_target, segments, nullptr, out, flags);
+    const uint64_t toff[2] = {0, n_target};
+    return proof_entry(s, "trim_proof", nullptr, 0, path, ProofTargets{target, toff, 1, nullptr}, segments, nullptr, out, flags);
 }
 
 static int trim_result(mi355sat* s) {
@@ -4307,7 +4448,7 @@ int mi355sat_solve(mi355sat* s) {
 int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* assump_offsets, uint64_t n_instances,
                          int32_t* results_out, int stop_at_first) {
     if (!s || !assump_offsets || !results_out || n_instances == 0) return MI355SAT_ERR_ARG;
-    return guarded(s, GUARD_TIMED, [&] {
+    const int rc = guarded(s, GUARD_TIMED, [&] {
         std::vector<int32_t> assump, results, winner;
         std::vector<uint64_t> aoff;
         copy_lists(assumps, assump_offsets, n_instances, assump, aoff);
@@ -4325,6 +4466,8 @@ int mi355sat_solve_batch(mi355sat* s, const int32_t* assumps, const uint64_t* as
         }
         return 0;
     });
+    proof_close(*s, false);      // (the core lines are in it: proof_core_lines; after an error it ends where the error came)
+    return rc;
 }
 
 int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64_t* decision_offsets,
@@ -4387,22 +4530,26 @@ int mi355sat_propagate_batch(mi355sat* s, const int32_t* decisions, const uint64
 
 int mi355sat_sweep_begin(mi355sat* s, const int32_t* assumps, const uint64_t* assump_offsets, uint64_t n_instances) {
     if (!s || !assump_offsets || n_instances == 0) return MI355SAT_ERR_ARG;
-    return guarded(s, GUARD_DEVICE, [&] {
+    const int rc = guarded(s, GUARD_DEVICE, [&] {
         std::vector<int32_t> assump;
         std::vector<uint64_t> aoff;
         copy_lists(assumps, assump_offsets, n_instances, assump, aoff);
+        proof_close(*s, false);                          // (of a sweep this one replaces)
         delete s->sweep;
         s->sweep = new SweepHolder;
         s->sweep->base = s->stats;
         s->trim.drop();
         go_cold(*s, MI355SAT_COLD_OTHER_SEARCH);
+        s->sweep->sw.cores = !s->proof_path.empty();     // final-conflict cores only while a proof is logged: its core lines
         return sweep_begin(*s, s->sweep->sw, assump, aoff, (uint32_t)n_instances, false);
     });
+    if (rc < 0) proof_close(*s, false);
+    return rc;
 }
 
 int mi355sat_sweep_step(mi355sat* s, int32_t* results_out, uint64_t* n_decided) {
     if (!s || !s->sweep) return MI355SAT_ERR_STATE;
-    return guarded(s, GUARD_TIMED, [&] {
+    const int step_rc = guarded(s, GUARD_TIMED, [&] {
         Sweep& sw = s->sweep->sw;
         int rc = sweep_step(*s, sw);
         if (results_out) for (uint32_t i = 0; i < sw.n_instances; i++) results_out[i] = sw.results[i];
@@ -4418,6 +4565,8 @@ int mi355sat_sweep_step(mi355sat* s, int32_t* results_out, uint64_t* n_decided) 
         accumulate_stats(*s, sw.sts);
         return rc;
     });
+    if (step_rc < 0) proof_close(*s, false);     // the file ends where the error came, as a failed solve()'s
+    return step_rc;
 }
 
 int mi355sat_sweep_drop(mi355sat* s, const uint64_t* instances, uint64_t n) {
@@ -4470,8 +4619,24 @@ int mi355sat_sweep_model_of(mi355sat* s, uint64_t instance, int8_t* out, uint64_
     });
 }
 
+int mi355sat_sweep_core_of(mi355sat* s, uint64_t instance, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (!s) return MI355SAT_ERR_ARG;
+    if (!s->sweep || !s->sweep->sw.log_cores) { s->err = "no core: no sweep that logs a proof is running"; return MI355SAT_ERR_STATE; }
+    const Sweep& sw = s->sweep->sw;
+    if (instance >= sw.n_instances || sw.results[instance] != MI355SAT_UNSAT) {
+        s->err = "no core: instance out of range or not UNSAT in this sweep";
+        return instance >= sw.n_instances ? MI355SAT_ERR_ARG : MI355SAT_ERR_STATE;
+    }
+    return guarded(s, GUARD_HOST, [&] {
+        Core core;
+        core.lits = sw.core_of((uint32_t)instance);
+        return copy_core(s, core, out, cap, n);
+    });
+}
+
 int mi355sat_sweep_end(mi355sat* s) {
     if (!s || !s->sweep) return MI355SAT_ERR_STATE;
+    proof_close(*s, false);
     return guarded(s, GUARD_DEVICE, [&] {
         Sweep& sw = s->sweep->sw;
         s->batch_models.assign(sw.n_instances, {});
@@ -4635,6 +4800,7 @@ int mi355sat_share_import(mi355sat* s, const int32_t* clauses, uint64_t n_words,
     if (!s || (!clauses && n_words)) return MI355SAT_ERR_ARG;
     if (n_records) *n_records = 0;
     if (!n_words || !s->share_slots || !s->d_share_pool.p || !s->sweep) return 0;
+    if (s->proof_file) return 0;                       // a foreign clause has no derivation in the proof being logged
     return guarded(s, GUARD_DEVICE, [&] {
         std::vector<uint8_t> gone(s->n_vars, 0);       // variables this handle's simplification resolved away
         for (const MsElim& e : s->elims) if ((uint32_t)(e.x >> 1) < gone.size()) gone[e.x >> 1] = 1;

@@ -130,6 +130,10 @@ class Mi355SatProofInfo(ctypes.Structure):   # mi355sat_proof_info
         return d
 
 
+class Mi355SatProofLogInfo(ctypes.Structure):   # mi355sat_proof_log_info
+    _fields_ = [(n, ctypes.c_uint64) for n in ("drains", "gathers", "logs", "words", "core_lines")] + [("drain_seconds", ctypes.c_double)]
+
+
 class Mi355SatTrimInfo(ctypes.Structure):   # mi355sat_trim_info
     _fields_ = [("check", Mi355SatProofInfo)] + \
                [(n, ctypes.c_uint64) for n in ("core_clauses", "lemmas_needed", "dep_records", "log_drains", "log_words_per_worker")]
@@ -251,6 +255,12 @@ def _bind(L):
                                                    ctypes.c_int32, ctypes.POINTER(Mi355SatSearchBuild)]
     L.mi355sat_check_proof.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
     L.mi355sat_check_proof_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Mi355SatProofInfo)]
+    L.mi355sat_check_proof_targets.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.c_uint32, vp,
+                                               ctypes.POINTER(Mi355SatProofInfo)]
+    L.mi355sat_check_proof_targets_file.argtypes = [vp, ctypes.c_char_p, vp, vp, ctypes.c_uint64, ctypes.c_uint32, vp,
+                                                    ctypes.POINTER(Mi355SatProofInfo)]
+    L.mi355sat_sweep_core_of.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.mi355sat_debug_proof_log.argtypes = [vp, ctypes.POINTER(Mi355SatProofLogInfo)]
     L.mi355sat_debug_proof_check_chunk.argtypes = [vp, ctypes.c_uint32]
     L.mi355sat_proof_deletions.argtypes = [vp, ctypes.c_int]
     L.mi355sat_debug_proof_deletions.argtypes = [vp, ctypes.POINTER(Mi355SatProofDelInfo)]
@@ -437,6 +447,41 @@ class Mi355Sat:
                                                       ctypes.byref(info)), "check_proof_file")
         return info.as_dict()
 
+    @staticmethod
+    def _target_lists(targets):
+        targets = [list(t) for t in targets]
+        offs = np.zeros(len(targets) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(t) for t in targets])
+        flat = np.asarray([l for t in targets for l in t], dtype=np.int32)
+        return flat, offs, np.zeros(max(1, len(targets)), dtype=np.int32)
+
+    def check_proof_targets(self, proof, targets, segments=0):
+        """check_proof() for several targets in one pass - what certifies every UNSAT verdict of a batch or a sweep from
+        the one file it logged: `targets` is a list of clauses, each checked against the formula and ALL lemmas of `proof`
+        (targets do not see each other).  Returns check_proof's dict ("valid": every lemma and every target passes;
+        "first_failed" counts target t as n_lemmas + t) plus "target_valid": per target 1 (RUP, a tautology, or the
+        database is refuted by then), 0, or -1 after an interrupt."""
+        pr = np.ascontiguousarray(proof, dtype=np.int32)
+        flat, offs, valid = self._target_lists(targets)
+        info = Mi355SatProofInfo()
+        self._check(self._L.mi355sat_check_proof_targets(self._h, _p(pr), pr.size, _p(flat), _p(offs), len(offs) - 1, int(segments),
+                                                         _p(valid), ctypes.byref(info)), "check_proof_targets")
+        return dict(info.as_dict(), target_valid=[int(v) for v in valid[:len(offs) - 1]])
+
+    def check_proof_targets_file(self, path, targets, segments=0):
+        """The same for a DRUP text file as set_proof_path() writes it."""
+        flat, offs, valid = self._target_lists(targets)
+        info = Mi355SatProofInfo()
+        self._check(self._L.mi355sat_check_proof_targets_file(self._h, str(path).encode(), _p(flat), _p(offs), len(offs) - 1,
+                                                              int(segments), _p(valid), ctypes.byref(info)), "check_proof_targets_file")
+        return dict(info.as_dict(), target_valid=[int(v) for v in valid[:len(offs) - 1]])
+
+    def debug_proof_log(self):
+        """Test hook: mi355sat_proof_log_info of the proof file open now or closed last, as a dict."""
+        info = Mi355SatProofLogInfo()
+        self._check(self._L.mi355sat_debug_proof_log(self._h, ctypes.byref(info)), "debug_proof_log")
+        return {n: getattr(info, n) for n, _ in info._fields_}
+
     def debug_proof_check_chunk(self, max_lemmas_per_launch=0):
         """Test hook: at most this many lemmas per worker and launch of check_proof (0 = the default, time-bounded)."""
         self._check(self._L.mi355sat_debug_proof_check_chunk(self._h, int(max_lemmas_per_launch)), "debug_proof_check_chunk")
@@ -616,6 +661,11 @@ class Mi355Sat:
         self._check(self._L.mi355sat_sweep_model_of(self._h, instance, _p(out), n_vars), "sweep_solution_of")
         return out
 
+    def sweep_core_of(self, instance):
+        """The core of an instance that already reported Unsat, while a sweep that logs a proof (set_proof_path) is
+        running; SolverError in any other state - a sweep computes cores only for its proof's sake."""
+        return self._core(self._L.mi355sat_sweep_core_of, instance)
+
     def sweep_end(self):
         self._check(self._L.mi355sat_sweep_end(self._h), "sweep_end")
 
@@ -717,8 +767,13 @@ class Mi355Sat:
         return nr.value
 
     def set_proof_path(self, path):
-        """DRUP proof of the next plain solve(), in its default configuration: all workers, clause exchange on (one log per
-        worker, drained after every slice)."""
+        """DRUP proof of the next solve(), solve_batch() or sweep_begin() .. sweep_end(), in its default configuration: all
+        workers, clause exchange on (one log per worker, drained after every slice with one kernel and one copy).  A batch
+        or a sweep writes ONE file: the lemmas of all workers of all instances, and behind the slice that decides an
+        instance Unsat the clause of its negated core (core_of / sweep_core_of), so that check_proof_targets_file() with
+        the negated cores as targets certifies every Unsat verdict in one pass and trim_proof_file() works per instance.
+        The empty clause is written at most once, nothing for a tautological core; share_import() takes no record while
+        a proof is logged.  The file is closed when the call ends (sweep_end for a sweep).  include/mi355sat.h."""
         self._check(self._L.mi355sat_set_proof_path(self._h, path.encode() if path else None), "set_proof_path")
 
     def set_incremental(self, on=True):
